@@ -16,8 +16,14 @@ feature pass, FDS.update_last_epoch_stats and FDS.update_running_stats (with the
 N > 1). `value` counts trained images only (K * B * N / time), so it is the throughput of the whole loop, tail included;
 `train_only_images_per_sec` is the same clock without the tail.
 
-Rank 0 prints ONE JSON line of at most 6 KB (a 20 KB line was not parsed by the driver) and writes the untrimmed result to
-gpurun_out/bench_detail.json. After the timed region, rank 0 at N=1 also measures (none of it inside `value`):
+Rank 0 prints ONE JSON line of at most 6 KB (a 20 KB line was not parsed by the driver). A plain run does nothing else: set-up,
+warm-up, the K timed steps, `--dump-outputs DIR` when given, the line (`metric`, `value`, `unit`, `ms_per_step` = wall time of the timed
+region / K, `higher_is_better`, `dtype`, ...). `--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy
+(float32): the loss of the last step, the FDS buffers after the last epoch tail, the encodings of that tail and the parameters (fixed, seeded
+samples of the two large ones; under 40 MB in all). The inputs are seeded, so two builds run with the same arguments see the same data.
+
+`--full` adds everything below and writes the untrimmed result to the --detail file. After the timed region it times the same steps without
+the tail (`train_only_images_per_sec`), and rank 0 at N=1 also measures (none of it inside `value`):
   * `roofline` — the dominant kernel family, the MFMA implicit-GEMM convolution (conv_igemm_*: 52 forward + 49 stride-1 /
     compact data-gradient + 12 parity-class launches per step), IN SITU: per-kernel device times of whole training steps
     from the profiler's kernel trace (the same numbers `rocprofv3 --kernel-trace` of this command reports;
@@ -27,7 +33,7 @@ gpurun_out/bench_detail.json. After the timed region, rank 0 at N=1 also measure
     an HBM-resident size, the NYUD2 narrow-row scatter, each with algorithmic bytes / FLOPs from SURVEY.md §8d;
   * `roofline_step` — the per-step floor (sum of per-kernel rooflines) at nominal and measured peaks;
   * `cpu_baseline` — the reference's own loop (or its pinned torch-CPU port where /root/reference is absent) on the host cores at B=8.
-`--extras` (minutes; tools/bench_extras.py) adds to the detail file: every conv shape alone (`conv_layers`), all FDS shapes, the float32 modes (exact / split-bf16 x3 / x2),
+`--extras` (minutes; tools/bench_extras.py; implies --full) adds to the detail file: every conv shape alone (`conv_layers`), all FDS shapes, the float32 modes (exact / split-bf16 x3 / x2),
 the real-file input pipeline, the vendor-library step, the CPU micro-baselines.
 """
 import argparse
@@ -458,6 +464,56 @@ def self_spawn(args):
     return subprocess.run(cmd, env=env).returncode
 
 
+def headline(args, world, dt, loss_val):
+    """The fields of the line a plain run prints: the throughput of the timed region and what was timed."""
+    images = args.steps * args.batch * world
+    flops = args.steps * args.batch * FLOP_FWD_BWD + args.steps * args.batch * FLOP_FWD   # per GPU: one tail forward per trained batch
+    result = {
+        "metric": "images/sec ResNet-50+FDS IMDB-WIKI 224x224 (train loop incl. FDS epoch tail)",
+        "value": images / dt, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic" if not args.share_gpu else "synthetic (TEST RUN: all ranks share one GPU, number meaningless)",
+        "config": {"workload": "BASELINE configs[1]: IMDB-WIKI-DIR ResNet-50 + LDS + FDS (ks=5, sigma=2), bf16 MFMA conv stack, fp32 BatchNorm statistics / FDS tail / "
+                               "loss, batch 256 per MI355X, l1, Adam 1e-3; one epoch-tail forward per trained batch + FDS update per bench epoch inside the timed region"
+                               + ("" if world == 1 else f"; configs[2] form: {world} ranks, RCCL gradient all-reduce per step + FDS statistic all-reduce per epoch tail"),
+                   "per_gpu_batch": args.batch, "global_batch": args.batch * world, "epoch_len_steps": args.epoch_len,
+                   "tail_forward_batches_in_timed_region": args.steps, "parallelism": f"dp{world}", "final_loss": loss_val},
+        # whole-loop MFMA fraction (24.287 GFLOP per trained image + 8.174 per tail-forward image over the wall clock)
+        "roofline_loop": {"bound": "mfma", "kernel": "whole train loop per GPU: ResNet-50 fwd+bwd (+ fwd-only epoch tail)",
+                          "achieved": flops / dt / 1e12, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                          "frac": flops / dt / 1e12 / PEAK_BF16_TFLOPS},
+    }
+    result["roofline"] = dict(result["roofline_loop"], traffic=None)
+    return result
+
+
+DUMP_PARAM_SAMPLE = 1 << 22       # parameter elements written by --dump-outputs (of 23.5 M), fixed seeded positions
+DUMP_FEATURE_ROWS = 2048          # epoch-tail encodings written by --dump-outputs (rows of [N, 2048]), fixed seeded rows
+
+
+def dump_outputs(out_dir, model, loss, store):
+    """What the timed path computed in its last step, as out_dir/<name>.npy (float32, under 40 MB in all): the loss of the last
+    step, the FDS buffers after the last epoch tail (full), the encodings that tail fed to FDS.update_running_stats and their labels
+    (a fixed, seeded sample of rows) and the trained parameters (a fixed, seeded sample of the flattened parameter vector, in
+    named_parameters() order). The sample positions depend only on the shapes, so two builds are compared element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy().astype(np.float32))
+    save("loss", loss.reshape(1))
+    for name, buf in model.FDS.named_buffers():
+        save("fds_" + name, buf)
+    feats, labels = store.view()
+    rows = np.sort(np.random.default_rng(7).permutation(feats.shape[0])[:DUMP_FEATURE_ROWS])
+    rows_t = torch.as_tensor(rows, device=feats.device)
+    save("tail_features_sample", feats.index_select(0, rows_t))
+    save("tail_labels_sample", labels.index_select(0, rows_t))
+    flat = torch.cat([p.detach().float().reshape(-1) for _, p in model.named_parameters()])
+    idx = np.sort(np.random.default_rng(8).choice(flat.numel(), size=min(DUMP_PARAM_SAMPLE, flat.numel()), replace=False))
+    save("params_sample", flat.index_select(0, torch.as_tensor(idx, device=flat.device)))
+    torch.cuda.synchronize()
+
+
 def compact(o, sig=5):
     """Floats to `sig` significant digits, recursively (the line the driver parses stays short; the detail file keeps full precision)."""
     if isinstance(o, float):
@@ -510,22 +566,29 @@ def driver_line(result):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=24)
+    ap.add_argument("--steps", type=int, default=24, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch")
     ap.add_argument("--epoch-len", type=int, default=8, help="steps per bench epoch (one FDS epoch tail each)")
     ap.add_argument("--backend", default=None, choices=[None, "nccl", "gloo"], help="torch.distributed backend (default: nccl = RCCL)")
     ap.add_argument("--share-gpu", action="store_true", help="TEST ONLY: every rank uses cuda:0 (with --backend gloo), to run the N > 1 "
                     "control flow on a one-GPU box; the throughput it prints is meaningless")
-    ap.add_argument("--extras", action="store_true", help="rank 0 also runs tools/bench_extras.py (every conv layer alone, all FDS shapes, float32 modes (exact / split x3 / x2), "
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure everything beyond the headline figure: train-only "
+                    "steps, communication report (N > 1 or --force-collectives), in-situ kernel breakdown, roofline, PMC traffic, kernel rooflines, CPU "
+                    "baseline; and write the --detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step to DIR/<name>.npy")
+    ap.add_argument("--extras", action="store_true", help="(implies --full) rank 0 also runs tools/bench_extras.py (every conv layer alone, all FDS shapes, float32 modes (exact / split x3 / x2), "
                     " input pipeline, vendor-library step, CPU micro-baselines: minutes) and writes them to the detail file")
     ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"), help="where the untrimmed result goes")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-rooflines", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child passes (roofline.traffic: the last committed pass)")
     ap.add_argument("--force-collectives", action="store_true", help="N = 1 only: run the loop through the engine's N > 1 branch in a ONE-rank nccl (RCCL) "
-                    "group — gradient hooks, bucket all-reduces, FDS statistic merge — to price that machinery on one GPU (`comm` object in the line)")
+                    "group — gradient hooks, bucket all-reduces, FDS statistic merge — to price that machinery on one GPU (`comm` object in the line with --full)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    args.full = args.full or args.extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_spawn(args))
@@ -571,29 +634,24 @@ def main():
     loss_val = float(loss.item())
     log(f"timed region done: {dt:.2f}s for {args.steps} steps")
     assert np.isfinite(loss_val) and loss_val < 1e6, f"Loss explosion: {loss_val}"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss, store)
+        log(f"outputs written to {args.dump_outputs}")
+    if not args.full:
+        if world > 1 or forced:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (driver_line(headline(args, world, dt, loss_val)) + "\n").encode())
+        return
     # same steps without the tail (for the plain-ResNet comparison and the MFMA fraction of the step itself)
     dt_train, _ = timed(lambda: run_steps(engine, optimizer, batches, store, args.steps, args.epoch_len, epoch, loss_fn, with_tail=False),
                         device, world)
 
-    images = args.steps * args.batch * world
-    flops = args.steps * args.batch * FLOP_FWD_BWD + args.steps * args.batch * FLOP_FWD   # per GPU: one tail forward per trained batch
-    result = {
-        "metric": "images/sec ResNet-50+FDS IMDB-WIKI 224x224 (train loop incl. FDS epoch tail)",
-        "value": images / dt, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16", "data": "synthetic" if not args.share_gpu else "synthetic (TEST RUN: all ranks share one GPU, number meaningless)",
-        "config": {"workload": "BASELINE configs[1]: IMDB-WIKI-DIR ResNet-50 + LDS + FDS (ks=5, sigma=2), bf16 MFMA conv stack, fp32 BatchNorm statistics / FDS tail / "
-                               "loss, batch 256 per MI355X, l1, Adam 1e-3; one epoch-tail forward per trained batch + FDS update per bench epoch inside the timed region"
-                               + ("" if world == 1 else f"; configs[2] form: {world} ranks, RCCL gradient all-reduce per step + FDS statistic all-reduce per epoch tail"),
-                   "per_gpu_batch": args.batch, "global_batch": args.batch * world, "epoch_len_steps": args.epoch_len,
-                   "tail_forward_batches_in_timed_region": args.steps, "parallelism": f"dp{world}", "final_loss": loss_val},
-        "train_only_images_per_sec": images / dt_train,
-        # whole-loop MFMA fraction (24.287 GFLOP per trained image + 8.174 per tail-forward image over the wall clock)
-        "roofline_loop": {"bound": "mfma", "kernel": "whole train loop per GPU: ResNet-50 fwd+bwd (+ fwd-only epoch tail)",
-                          "achieved": flops / dt / 1e12, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                          "frac": flops / dt / 1e12 / PEAK_BF16_TFLOPS,
-                          "train_only_frac": args.steps * args.batch * FLOP_FWD_BWD / dt_train / 1e12 / PEAK_BF16_TFLOPS},
-    }
+    result = headline(args, world, dt, loss_val)
+    result["train_only_images_per_sec"] = args.steps * args.batch * world / dt_train
+    result["roofline_loop"]["train_only_frac"] = args.steps * args.batch * FLOP_FWD_BWD / dt_train / 1e12 / PEAK_BF16_TFLOPS
     result["roofline"] = dict(result["roofline_loop"], traffic=None)      # replaced below by the dominant kernel's when measured
     # ---- measurements that still need every rank (collectives inside the steps): communication report, in-situ kernel times
     if world > 1 or forced:

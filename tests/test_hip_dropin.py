@@ -400,7 +400,7 @@ def test_bench_multi_rank_control_flow_two_processes_one_gpu(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     detail = str(tmp_path / "bench_detail.json")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--batch", "16",
-           "--epoch-len", "2", "--backend", "gloo", "--share-gpu", "--detail", detail]
+           "--epoch-len", "2", "--backend", "gloo", "--share-gpu", "--full", "--detail", detail]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

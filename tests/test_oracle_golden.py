@@ -119,28 +119,18 @@ def test_losses(golden):
                 assert relerr(grad, ref_g, floor=1e-3 * float(np.abs(ref_g).max())) < 1e-5, (b, kind, extra, use_w)
 
 
-@pytest.mark.needs_reference
-def test_oracle_vs_live_reference_random():
-    """Extra pin when /root/reference is present: random FDS sequences vs the live reference."""
-    import torch
-    from oracle import refshim
-    rng = np.random.default_rng(42)
+def test_oracle_vs_live_reference_random(golden):
+    """Random FDS sequences (three configurations, four epochs each) vs the reference's buffers, recorded from the live reference
+    by tests/golden/gen_golden_pins.py."""
+    g = golden("fds_live_random.npz")
     for trial in range(3):
-        start, num, c, n = int(rng.integers(0, 4)), int(rng.integers(12, 60)), 16, 300
-        kw = dict(feature_dim=c, bucket_num=num, bucket_start=start, start_update=0, start_smooth=1,
-                  kernel="gaussian", ks=5, sigma=2, momentum=0.9)
-        R = refshim.make_fds(**kw)
+        kw = json.loads(str(g[f"t{trial}_kw"]))
         O = fds_oracle.FDSOracle(**kw)
         for epoch in range(4):
-            labels = np.clip(np.round(rng.normal(num / 2, num / 3, n)), 0, num + 4).astype(np.float32)
-            feats = rng.normal(0.5, 0.3, (n, c)).astype(np.float32)
-            with refshim.cuda_identity():
-                R.update_last_epoch_stats(epoch)
-                R.update_running_stats(torch.tensor(feats), torch.tensor(labels), epoch)
             O.update_last_epoch_stats(epoch)
-            O.update_running_stats(feats, labels, epoch)
+            O.update_running_stats(g[f"t{trial}_e{epoch}_in_feats"], g[f"t{trial}_e{epoch}_in_labels"], epoch)
             for k in BUFFERS:
-                assert_close(getattr(O, k), getattr(R, k).numpy(), msg=f"{trial} {epoch} {k}")
+                assert_close(getattr(O, k), g[f"t{trial}_e{epoch}_ref_{k}"], msg=f"{trial} {epoch} {k}")
 
 
 # ---- STS-B FDS variant (SURVEY.md §8f-2) -----------------------------------------------------------------

@@ -56,27 +56,32 @@ def test_emulated_block_rounds_where_the_product_stores():
     assert is_bf16(y.detach())
 
 
-@pytest.mark.needs_reference
-def test_emulation_on_the_port_equals_emulation_on_the_live_reference():
-    """The GPU box has no /root/reference: the teacher-forced bf16 test runs the emulation on oracle.torch_oracle's port of the
-    block. Here the same emulation on the reference's OWN Bottleneck (same weights, same input): identical float64 outputs and
-    input gradients."""
-    from oracle import refshim
-    ref = refshim.load("imdb-wiki-dir")
+def bf16_block_run():
+    """The emulation on oracle.torch_oracle's port of the block, on the recorded weights, input and upstream gradient."""
+    import os
+    g = np.load(os.path.join(GOLDEN, "bf16_block_ref.npz"))
+    from oracle.bf16_emul import bf16_points
+    from oracle.torch_oracle import _Bottleneck
+    ds = torch.nn.Sequential(torch.nn.Conv2d(64, 128, 1, 2, bias=False), torch.nn.BatchNorm2d(128))
+    ob = _Bottleneck(64, 32, 2, ds).double()
+    ob.load_state_dict({k[2:]: torch.from_numpy(g[k]) for k in g.files if k.startswith("w_")})
+    assert len(bf16_points(ob)) == 4 + 2 + 1
+    xa = torch.from_numpy(g["in_x"]).requires_grad_(True)
+    ya = ob.train()(xa)
+    ya.backward(torch.from_numpy(g["in_g"]))
+    return {"y": ya.detach().numpy(), "gx": xa.grad.numpy()}
 
-    def make(ob):
-        ds = torch.nn.Sequential(torch.nn.Conv2d(64, 128, 1, 2, bias=False), torch.nn.BatchNorm2d(128))
-        rb = ref.resnet.Bottleneck(64, 32, 2, ds).double()
-        rb.load_state_dict(ob.state_dict())
-        return rb
-    ob, rb = _block_pair(make)
-    x = torch.randn(3, 64, 8, 8, dtype=torch.float64).float().bfloat16().double()
-    xa, xb = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
-    ya, yb = ob.train()(xa), rb.train()(xb)
-    assert torch.equal(ya, yb)
-    g = torch.randn_like(ya)
-    ya.backward(g); yb.backward(g)
-    assert torch.equal(xa.grad, xb.grad)
+
+def test_emulation_on_the_port_equals_emulation_on_the_live_reference(golden, tmp_path):
+    """The teacher-forced bf16 test runs the emulation on oracle.torch_oracle's port of the block. Here the same emulation on the
+    port against the reference's OWN Bottleneck under it (same weights, same input; recorded from the live reference by
+    tests/golden/gen_golden_pins.py): identical float64 outputs and input gradients. Recording and check both run with the pinned
+    CPU arithmetic of tests/test_torch_oracle.py (child process), so the bits do not depend on the host's BLAS / vector kernels."""
+    from test_torch_oracle import run_pinned
+    g = golden("bf16_block_ref.npz")
+    got = run_pinned("test_round3_host.bf16_block_run", str(tmp_path / "block.npz"))
+    assert np.array_equal(got["y"], g["ref_y"])
+    assert np.array_equal(got["gx"], g["ref_gx"])
 
 
 def test_gradsink_registry_hands_out_fresh_bucket_views():
