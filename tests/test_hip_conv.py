@@ -414,7 +414,7 @@ def test_stem_conv_matches_fp32_reference(shape):
     tot = stats.double().sum(0)
     assert_close(tot[0].cpu().numpy(), yf.sum(dim=(0, 2, 3)).cpu().numpy(), rtol=1e-5, atol_scale=1e-5, msg="sum")
     assert_close(tot[1].cpu().numpy(), (yf * yf).sum(dim=(0, 2, 3)).cpu().numpy(), rtol=1e-5, atol_scale=1e-5, msg="sumsq")
-    # weight gradient flows (library kernel), and the packed weights follow an optimizer step
+    # weight gradient flows (dir_stem_conv_wgrad, held to float64 in test_hip_bn_exact.py), and the packed weights follow an optimizer step
     y.float().square().mean().backward()
     wr = conv.weight.detach().clone().requires_grad_(True)
     F.conv2d(x.to(torch.bfloat16).float(), wr, None, 2, 3).square().mean().backward()
