@@ -14,12 +14,32 @@
 // computes it outside the model (train.py:255) and its mean over the batch would need a grid-wide reduction here.
 // The float32 arithmetic is written out exactly as the unfused kernels do it (-ffp-contract=off), so encoding, dx and
 // the data gradients are bit-identical to the pool -> smooth -> linear chain they replace.
+//
+// Dropout (resnet.py:98-101,146-147: nn.Dropout(p) between FDS.smooth and the linear layer, training only): the three
+// kernels below take an optional trailing DirDropout argument (a parameter pack of zero or one element). Without it they
+// are the kernels above, unchanged; with it the linear layer reads drop(encoding) = keep ? encoding * scale : 0 with the
+// Philox mask of dir_rng.h, regenerated from (seed, offset) in the backward instead of stored. The stored encoding stays
+// the calibrated, pre-dropout tensor (the reference's `encoding`, A.2); the mask applies to pred, to the linear layer's
+// share of the data gradient and to dW.
 #include "dir_common.h"
+#include "dir_rng.h"
 
 namespace {
 
 __device__ __forceinline__ float tl_calib1(float x, float m1, float s, float m2) {
     return (s < 0.0f) ? x : (x - m1) * s + m2;               // utils.py:107; s < 0 = "leave untouched" (dir_fds_prepare_scale)
+}
+
+// drop() of the 8 channels g * 8 .. g * 8 + 7 of row `row`: elements e .. e + 7 with e % 8 == 0, two Philox calls
+__device__ __forceinline__ void tl_drop8(const DirDropout& d, int row, int C, int g, float (&v)[8]) {
+    const uint64_t q = ((uint64_t)row * (uint64_t)C + (uint64_t)g * 8u) >> 2;
+    const DirU32x4 r0 = dir_dropout_bits(d, q), r1 = dir_dropout_bits(d, q + 1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v[j] = dir_dropout_apply(d, r0.v[j], v[j]); v[4 + j] = dir_dropout_apply(d, r1.v[j], v[4 + j]); }
+}
+
+__device__ __forceinline__ uint32_t tl_pick(const DirU32x4& r, uint32_t k) {      // r.v[k] without a dynamically indexed array
+    return k == 0 ? r.v[0] : k == 1 ? r.v[1] : k == 2 ? r.v[2] : r.v[3];
 }
 
 template <typename T> struct TailIO;
@@ -54,12 +74,14 @@ template <> struct TailIO<float> {                            // float32 NHWC ma
     static __device__ __forceinline__ float spread(float g, int hw) { return g / (float)hw; }               // = dir_avgpool_f32_bwd
 };
 
-template <typename T>
+template <typename T, typename... Drop>
 __global__ void __launch_bounds__(DIR_TPB)
 tail_fwd_kernel(const T* __restrict__ x, const float* __restrict__ labels, const int32_t* __restrict__ bins_in, int B, int HW, int C,
                 float lo, float hi, const float* __restrict__ m1, const float* __restrict__ scale, const float* __restrict__ m2,
                 const float* __restrict__ weight, const float* __restrict__ bias, float* __restrict__ enc, float* __restrict__ pred,
-                int32_t* __restrict__ bins_out) {
+                int32_t* __restrict__ bins_out, const Drop... drop) {
+    constexpr bool kDrop = sizeof...(Drop) > 0;
+    const DirDropout dr{drop...};
     __shared__ float red[4];
     const int row = blockIdx.x, t = threadIdx.x;
     int bin = -1;
@@ -99,6 +121,9 @@ tail_fwd_kernel(const T* __restrict__ x, const float* __restrict__ labels, const
         float* o = enc + (size_t)row * C + g * 8;
         *reinterpret_cast<float4*>(o) = make_float4(e[0], e[1], e[2], e[3]);
         *reinterpret_cast<float4*>(o + 4) = make_float4(e[4], e[5], e[6], e[7]);
+        if constexpr (kDrop) {
+            tl_drop8(dr, row, C, g, e);                                        // (after the store: `encoding` is pre-dropout)
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) dot += e[j] * weight[g * 8 + j];
     }
@@ -109,19 +134,27 @@ tail_fwd_kernel(const T* __restrict__ x, const float* __restrict__ labels, const
     if (t == 0) pred[row] = ((red[0] + red[1]) + (red[2] + red[3])) + bias[0];
 }
 
-template <typename T>
+template <typename T, typename... Drop>
 __global__ void __launch_bounds__(DIR_TPB)
 tail_bwd_dx_kernel(const float* __restrict__ dpred, const float* __restrict__ denc, const int32_t* __restrict__ bins,
-                   const float* __restrict__ scale, const float* __restrict__ weight, int HW, int C, T* __restrict__ dx) {
+                   const float* __restrict__ scale, const float* __restrict__ weight, int HW, int C, T* __restrict__ dx,
+                   const Drop... drop) {
+    constexpr bool kDrop = sizeof...(Drop) > 0;
+    const DirDropout dr{drop...};
     const int row = blockIdx.x, t = threadIdx.x;
     const float dp = dpred[row];
     const int bin = bins ? bins[row] : -1;
     const int groups = C >> 3;
     for (int g = t; g < groups; g += DIR_TPB) {
         float v[8];
+        if constexpr (kDrop) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = dp * weight[g * 8 + j];
+            tl_drop8(dr, row, C, g, v);                                        // dropout backward: the same mask and scale
+        }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            float gr = dp * weight[g * 8 + j];                                 // d encoding_s = dpred * W (Linear backward)
+            float gr = kDrop ? v[j] : dp * weight[g * 8 + j];                  // d encoding_s = dpred * W (Linear backward)
             if (denc) gr += denc[(size_t)row * C + g * 8 + j];                  // + a gradient that reached the returned encoding
             if (bin >= 0) { const float s = scale[(size_t)bin * C + g * 8 + j]; gr = s < 0.0f ? gr : gr * s; }   // calibrate backward
             v[j] = TailIO<T>::spread(gr, HW);                                  // average-pool backward
@@ -131,16 +164,26 @@ tail_bwd_dx_kernel(const float* __restrict__ dpred, const float* __restrict__ de
     }
 }
 
-// partial[slice][c] = sum over the rows of the slice (in order) of dpred[b] * enc[b, c]
+// partial[slice][c] = sum over the rows of the slice (in order) of dpred[b] * enc[b, c]  (drop(enc[b, c]) with dropout)
+template <typename... Drop>
 __global__ void __launch_bounds__(DIR_TPB)
 tail_bwd_dw_partial_kernel(const float* __restrict__ dpred, const float* __restrict__ enc, int B, int C, int rows_per_slice,
-                           float* __restrict__ partial) {
+                           float* __restrict__ partial, const Drop... drop) {
+    constexpr bool kDrop = sizeof...(Drop) > 0;
+    const DirDropout dr{drop...};
     const int c = blockIdx.x * DIR_TPB + threadIdx.x;
     if (c >= C) return;
     const int b0 = blockIdx.y * rows_per_slice;
     const int b1 = (b0 + rows_per_slice < B) ? b0 + rows_per_slice : B;
     float s = 0.0f;
-    for (int b = b0; b < b1; ++b) s += dpred[b] * enc[(size_t)b * C + c];
+    for (int b = b0; b < b1; ++b) {
+        float v = enc[(size_t)b * C + c];
+        if constexpr (kDrop) {
+            const uint64_t e = (uint64_t)b * (uint64_t)C + (uint64_t)c;
+            v = dir_dropout_apply(dr, tl_pick(dir_dropout_bits(dr, e >> 2), (uint32_t)e & 3u), v);
+        }
+        s += dpred[b] * v;
+    }
     partial[(size_t)blockIdx.y * C + c] = s;
 }
 
@@ -171,6 +214,81 @@ int tail_slices(int B, int* rows_per_slice) {
     return (B + rps - 1) / rps;
 }
 
+// The entry points share one launcher per direction: `drop...` is empty (dir_tail_fwd / dir_tail_bwd, the kernels
+// without dropout) or one DirDropout (dir_tail_dropout_fwd / dir_tail_dropout_bwd).
+template <typename... Drop>
+int tail_fwd_launch(const void* x, int dtype, const float* labels, const int32_t* bins_in, int B, int HW, int C,
+                    int bucket_start, int bucket_num, const float* m1, const float* scale, const float* m2,
+                    const float* weight, const float* bias, float* encoding, float* pred, int32_t* bins_out,
+                    dir_stream_t stream, const Drop... drop) {
+    DIR_RETURN_IF(B < 0 || HW <= 0 || C <= 0, DIR_EINVAL);
+    if (B == 0) return DIR_OK;
+    DIR_RETURN_IF(!x || !weight || !bias || !encoding || !pred, DIR_EINVAL);
+    DIR_RETURN_IF(dtype != DIR_F32 && dtype != DIR_BF16, DIR_EUNSUPPORTED);
+    DIR_RETURN_IF(C % 8 != 0, DIR_EUNSUPPORTED);
+    DIR_RETURN_IF(!dir_aligned16(x) || !dir_aligned16(encoding), DIR_EINVAL);
+    const bool calibrate = m1 || scale || m2;
+    DIR_RETURN_IF(calibrate && (!m1 || !scale || !m2 || (!labels && !bins_in) || !bins_out), DIR_EINVAL);
+    DIR_RETURN_IF(calibrate && (bucket_start < 0 || bucket_num <= bucket_start), DIR_EINVAL);
+    const float lo = (float)bucket_start, hi = (float)(bucket_num - 1);
+    if (dtype == DIR_BF16)
+        hipLaunchKernelGGL((tail_fwd_kernel<uint16_t, Drop...>), dim3(B), dim3(DIR_TPB), 0, dir_s(stream), static_cast<const uint16_t*>(x),
+                           labels, bins_in, B, HW, C, lo, hi, m1, scale, m2, weight, bias, encoding, pred, bins_out, drop...);
+    else
+        hipLaunchKernelGGL((tail_fwd_kernel<float, Drop...>), dim3(B), dim3(DIR_TPB), 0, dir_s(stream), static_cast<const float*>(x),
+                           labels, bins_in, B, HW, C, lo, hi, m1, scale, m2, weight, bias, encoding, pred, bins_out, drop...);
+    DIR_LAUNCH_CHECK();
+    return DIR_OK;
+}
+
+bool dropout_p_ok(double p) { return p >= 0.0 && p <= 1.0; }                  // (false for NaN)
+
+template <typename... Drop>
+int tail_bwd_launch(const float* dpred, const float* dencoding, const int32_t* bins, const float* scale, const float* weight,
+                    const float* encoding, int B, int HW, int C, int dtype, void* dx, float* dweight, float* dbias,
+                    void* workspace, size_t workspace_bytes, dir_stream_t stream, const Drop... drop) {
+    DIR_RETURN_IF(B < 0 || HW <= 0 || C <= 0, DIR_EINVAL);
+    if (B == 0) return DIR_OK;
+    DIR_RETURN_IF(!dpred || !weight || (bins && !scale), DIR_EINVAL);
+    DIR_RETURN_IF(dtype != DIR_F32 && dtype != DIR_BF16, DIR_EUNSUPPORTED);
+    DIR_RETURN_IF(C % 8 != 0, DIR_EUNSUPPORTED);
+    if (dx) {
+        DIR_RETURN_IF(!dir_aligned16(dx), DIR_EINVAL);
+        if (dtype == DIR_BF16)
+            hipLaunchKernelGGL((tail_bwd_dx_kernel<uint16_t, Drop...>), dim3(B), dim3(DIR_TPB), 0, dir_s(stream), dpred, dencoding, bins,
+                               scale, weight, HW, C, static_cast<uint16_t*>(dx), drop...);
+        else
+            hipLaunchKernelGGL((tail_bwd_dx_kernel<float, Drop...>), dim3(B), dim3(DIR_TPB), 0, dir_s(stream), dpred, dencoding, bins,
+                               scale, weight, HW, C, static_cast<float*>(dx), drop...);
+        DIR_LAUNCH_CHECK();
+    }
+    if (dweight) {
+        DIR_RETURN_IF(!encoding || !workspace || workspace_bytes < dir_tail_bwd_workspace(B, C), DIR_EWORKSPACE);
+        int rps;
+        const int slices = tail_slices(B, &rps);
+        float* partial = static_cast<float*>(workspace);
+        hipLaunchKernelGGL((tail_bwd_dw_partial_kernel<Drop...>), dim3(dir_cdiv(C, DIR_TPB), slices), dim3(DIR_TPB), 0, dir_s(stream),
+                           dpred, encoding, B, C, rps, partial, drop...);
+        DIR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(tail_bwd_dw_final_kernel, dim3(dir_cdiv(C, DIR_TPB)), dim3(DIR_TPB), 0, dir_s(stream), partial, slices, dpred, B,
+                           C, dweight, dbias);
+        DIR_LAUNCH_CHECK();
+    }
+    return DIR_OK;
+}
+
+// keep[e] = 1 / 0 for the elements 4q .. 4q + 3 (< n) of one Philox call
+__global__ void __launch_bounds__(DIR_TPB)
+dropout_mask_kernel(const DirDropout d, int64_t n, uint8_t* __restrict__ keep) {
+    const int64_t q = (int64_t)blockIdx.x * DIR_TPB + threadIdx.x;
+    const int64_t e0 = q * 4;
+    if (e0 >= n) return;
+    const DirU32x4 r = dir_dropout_bits(d, (uint64_t)q);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (e0 + j < n) keep[e0 + j] = r.v[j] < d.thr ? 1 : 0;
+}
+
 }  // namespace
 
 extern "C" size_t dir_tail_bwd_workspace(int B, int C) {
@@ -183,55 +301,42 @@ extern "C" int dir_tail_fwd(const void* x, int dtype, const float* labels, const
                             int bucket_start, int bucket_num, const float* m1, const float* scale, const float* m2,
                             const float* weight, const float* bias, float* encoding, float* pred, int32_t* bins_out,
                             dir_stream_t stream) {
-    DIR_RETURN_IF(B < 0 || HW <= 0 || C <= 0, DIR_EINVAL);
-    if (B == 0) return DIR_OK;
-    DIR_RETURN_IF(!x || !weight || !bias || !encoding || !pred, DIR_EINVAL);
-    DIR_RETURN_IF(dtype != DIR_F32 && dtype != DIR_BF16, DIR_EUNSUPPORTED);
-    DIR_RETURN_IF(C % 8 != 0, DIR_EUNSUPPORTED);
-    DIR_RETURN_IF(!dir_aligned16(x) || !dir_aligned16(encoding), DIR_EINVAL);
-    const bool calibrate = m1 || scale || m2;
-    DIR_RETURN_IF(calibrate && (!m1 || !scale || !m2 || (!labels && !bins_in) || !bins_out), DIR_EINVAL);
-    DIR_RETURN_IF(calibrate && (bucket_start < 0 || bucket_num <= bucket_start), DIR_EINVAL);
-    const float lo = (float)bucket_start, hi = (float)(bucket_num - 1);
-    if (dtype == DIR_BF16)
-        hipLaunchKernelGGL(tail_fwd_kernel<uint16_t>, dim3(B), dim3(DIR_TPB), 0, dir_s(stream), static_cast<const uint16_t*>(x), labels,
-                           bins_in, B, HW, C, lo, hi, m1, scale, m2, weight, bias, encoding, pred, bins_out);
-    else
-        hipLaunchKernelGGL(tail_fwd_kernel<float>, dim3(B), dim3(DIR_TPB), 0, dir_s(stream), static_cast<const float*>(x), labels,
-                           bins_in, B, HW, C, lo, hi, m1, scale, m2, weight, bias, encoding, pred, bins_out);
-    DIR_LAUNCH_CHECK();
-    return DIR_OK;
+    return tail_fwd_launch(x, dtype, labels, bins_in, B, HW, C, bucket_start, bucket_num, m1, scale, m2, weight, bias, encoding, pred,
+                           bins_out, stream);
 }
 
 extern "C" int dir_tail_bwd(const float* dpred, const float* dencoding, const int32_t* bins, const float* scale, const float* weight,
                             const float* encoding, int B, int HW, int C, int dtype, void* dx, float* dweight, float* dbias,
                             void* workspace, size_t workspace_bytes, dir_stream_t stream) {
-    DIR_RETURN_IF(B < 0 || HW <= 0 || C <= 0, DIR_EINVAL);
-    if (B == 0) return DIR_OK;
-    DIR_RETURN_IF(!dpred || !weight || (bins && !scale), DIR_EINVAL);
-    DIR_RETURN_IF(dtype != DIR_F32 && dtype != DIR_BF16, DIR_EUNSUPPORTED);
-    DIR_RETURN_IF(C % 8 != 0, DIR_EUNSUPPORTED);
-    if (dx) {
-        DIR_RETURN_IF(!dir_aligned16(dx), DIR_EINVAL);
-        if (dtype == DIR_BF16)
-            hipLaunchKernelGGL(tail_bwd_dx_kernel<uint16_t>, dim3(B), dim3(DIR_TPB), 0, dir_s(stream), dpred, dencoding, bins, scale, weight,
-                               HW, C, static_cast<uint16_t*>(dx));
-        else
-            hipLaunchKernelGGL(tail_bwd_dx_kernel<float>, dim3(B), dim3(DIR_TPB), 0, dir_s(stream), dpred, dencoding, bins, scale, weight,
-                               HW, C, static_cast<float*>(dx));
-        DIR_LAUNCH_CHECK();
-    }
-    if (dweight) {
-        DIR_RETURN_IF(!encoding || !workspace || workspace_bytes < dir_tail_bwd_workspace(B, C), DIR_EWORKSPACE);
-        int rps;
-        const int slices = tail_slices(B, &rps);
-        float* partial = static_cast<float*>(workspace);
-        hipLaunchKernelGGL(tail_bwd_dw_partial_kernel, dim3(dir_cdiv(C, DIR_TPB), slices), dim3(DIR_TPB), 0, dir_s(stream), dpred, encoding,
-                           B, C, rps, partial);
-        DIR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(tail_bwd_dw_final_kernel, dim3(dir_cdiv(C, DIR_TPB)), dim3(DIR_TPB), 0, dir_s(stream), partial, slices, dpred, B,
-                           C, dweight, dbias);
-        DIR_LAUNCH_CHECK();
-    }
+    return tail_bwd_launch(dpred, dencoding, bins, scale, weight, encoding, B, HW, C, dtype, dx, dweight, dbias, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" int dir_tail_dropout_fwd(const void* x, int dtype, const float* labels, const int32_t* bins_in, int B, int HW, int C,
+                                    int bucket_start, int bucket_num, const float* m1, const float* scale, const float* m2,
+                                    const float* weight, const float* bias, float* encoding, float* pred, int32_t* bins_out,
+                                    uint64_t seed, uint64_t offset, double p, dir_stream_t stream) {
+    DIR_RETURN_IF(!dropout_p_ok(p), DIR_EINVAL);
+    return tail_fwd_launch(x, dtype, labels, bins_in, B, HW, C, bucket_start, bucket_num, m1, scale, m2, weight, bias, encoding, pred,
+                           bins_out, stream, dir_dropout_params(seed, offset, p));
+}
+
+extern "C" int dir_tail_dropout_bwd(const float* dpred, const float* dencoding, const int32_t* bins, const float* scale,
+                                    const float* weight, const float* encoding, int B, int HW, int C, int dtype, void* dx,
+                                    float* dweight, float* dbias, void* workspace, size_t workspace_bytes,
+                                    uint64_t seed, uint64_t offset, double p, dir_stream_t stream) {
+    DIR_RETURN_IF(!dropout_p_ok(p), DIR_EINVAL);
+    return tail_bwd_launch(dpred, dencoding, bins, scale, weight, encoding, B, HW, C, dtype, dx, dweight, dbias, workspace,
+                           workspace_bytes, stream, dir_dropout_params(seed, offset, p));
+}
+
+extern "C" int dir_dropout_mask(uint64_t seed, uint64_t offset, double p, int B, int C, uint8_t* keep, dir_stream_t stream) {
+    DIR_RETURN_IF(!dropout_p_ok(p) || B < 0 || C < 0, DIR_EINVAL);
+    const int64_t n = (int64_t)B * C;
+    if (n == 0) return DIR_OK;
+    DIR_RETURN_IF(!keep, DIR_EINVAL);
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(dir_cdiv((n + 3) / 4, DIR_TPB)), dim3(DIR_TPB), 0, dir_s(stream),
+                       dir_dropout_params(seed, offset, p), n, keep);
+    DIR_LAUNCH_CHECK();
     return DIR_OK;
 }

@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libdir_hip.so")
 c_int, c_float, c_double, c_void_p, c_size_t, c_int64 = (
     ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64)
 c_longlong = ctypes.c_longlong
+c_uint64 = ctypes.c_uint64
 DIR_EUNSUPPORTED = -2
 
 # name -> (restype, argtypes); must list every symbol of include/dir_hip.h
@@ -132,6 +133,11 @@ SIGNATURES = {
     "dir_tail_bwd_workspace": (c_size_t, [c_int, c_int]),
     "dir_tail_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dir_lds_weights": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "dir_tail_dropout_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 8
+                             + [c_uint64, c_uint64, c_double, c_void_p]),
+    "dir_tail_dropout_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
+                             + [c_uint64, c_uint64, c_double, c_void_p]),
+    "dir_dropout_mask": (c_int, [c_uint64, c_uint64, c_double, c_int, c_int, c_void_p, c_void_p]),
 }
 
 ABI_VERSION = 4

@@ -13,7 +13,7 @@ forward, stride-1 / stride-2 data gradients, weight gradient; BatchNorm statisti
 (``dirhip.pool``). Parity mode (no autocast, float32 activations): the SAME graph with the exact-float32 MFMA convolutions
 and pools of ``dirhip.conv_f32`` (``dir_conv_f32_*``) in place of the bf16 ones. No library convolution, BatchNorm or
 pooling call exists on either path; shapes the bf16 kernels do not take fall back to the float32 kernels, never to a library.
-The pool -> FDS calibrate -> linear -> weighted-loss tail is hand-written HIP and always fp32. GPU only (no CPU fallback).
+The pool -> FDS calibrate (-> dropout) -> linear -> weighted-loss tail is hand-written HIP and always fp32. GPU only (no CPU fallback).
 """
 import logging
 import math
@@ -205,10 +205,11 @@ class ResNet(nn.Module):
         smooth = bool(self.training and self.fds and epoch >= self.start_smooth)
         # the pool / FDS / linear / loss tail is fp32 whatever precision the conv stack ran in
         with torch.autocast(device_type=fmap.device.type, enabled=False):
-            if not self.use_dropout and tail_fusable(fmap, self.avgpool, self.linear):
-                # pool -> FDS.smooth -> linear as ONE kernel; `encoding` is the calibrated tensor (in the reference smooth()
-                # is in place and the same object is returned, A.2)
-                x, encoding = tail_forward(fmap, self.linear, self.FDS if smooth else None, targets)
+            if tail_fusable(fmap, self.avgpool, self.linear):
+                # pool -> FDS.smooth (-> dropout) -> linear as ONE kernel; `encoding` is the calibrated tensor (in the reference
+                # smooth() is in place and the same object is returned, A.2), before dropout (nn.Dropout is not in place)
+                p = self.dropout.p if self.training and self.use_dropout else None
+                x, encoding = tail_forward(fmap, self.linear, self.FDS if smooth else None, targets, dropout=p)
             else:
                 encoding = global_avgpool_flat(fmap, self.avgpool)
                 if encoding.dtype != torch.float32:

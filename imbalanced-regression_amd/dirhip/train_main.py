@@ -59,6 +59,7 @@ def build_parser(dataset_default='imdb_wiki'):
     # re-weighting / two-stage
     p.add_argument('--reweight', type=str, default='none', choices=['none', 'sqrt_inv', 'inverse'], help='cost-sensitive reweighting scheme')
     p.add_argument('--retrain_fc', action='store_true', default=False, help='whether to retrain last regression layer (regressor)')
+    p.add_argument('--dropout', type=float, default=None, help='dropout probability before the regressor (resnet50(dropout=); a Philox mask, not the random stream of nn.Dropout)')
     # training / optimisation
     p.add_argument('--dataset', type=str, default=dataset_default, choices=['imdb_wiki', 'agedb'], help='dataset name')
     p.add_argument('--data_dir', type=str, default='./data', help='data directory')
@@ -108,7 +109,7 @@ def build_parser(dataset_default='imdb_wiki'):
 
 
 def make_store_name(args):
-    """train.py:78-93."""
+    """train.py:78-93 (+ `_dropout_{P}` with --dropout, which the reference CLI does not have)."""
     name = f'_{args.store_name}' if len(args.store_name) else ''
     if not args.lds and args.reweight != 'none':
         name += f'_{args.reweight}'
@@ -123,6 +124,8 @@ def make_store_name(args):
         name += f'_{args.start_update}_{args.start_smooth}_{args.fds_mmt}'
     if args.retrain_fc:
         name += '_retrain_fc'
+    if args.dropout is not None:
+        name += f'_dropout_{args.dropout}'
     return f"{args.dataset}_{args.model}{name}_{args.optimizer}_{args.loss}_{args.lr}_{args.batch_size}"
 
 
@@ -389,7 +392,8 @@ def run(argv=None, dataset_default='imdb_wiki'):
     print('=====> Building model...')
     model = resnet50(fds=args.fds, bucket_num=args.bucket_num, bucket_start=args.bucket_start,
                      start_update=args.start_update, start_smooth=args.start_smooth,
-                     kernel=args.fds_kernel, ks=args.fds_ks, sigma=args.fds_sigma, momentum=args.fds_mmt)
+                     kernel=args.fds_kernel, ks=args.fds_ks, sigma=args.fds_sigma, momentum=args.fds_mmt,
+                     dropout=args.dropout)
     fp32_first = args.amp != 'bf16' or (args.amp_switch_epoch is not None and args.start_epoch < args.amp_switch_epoch)
     arith_of = {'fp32': 'exact', 'fp32x3': 'x3', 'fp32x2': 'x2'}
     f32_arith = arith_of[args.amp] if args.amp != 'bf16' else arith_of[args.amp_early]

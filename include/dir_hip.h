@@ -617,6 +617,29 @@ int dir_tail_bwd(const float* dpred, const float* dencoding, const int32_t* bins
                  const float* encoding, int B, int HW, int C, int dtype, void* dx, float* dweight, float* dbias,
                  void* workspace, size_t workspace_bytes, dir_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dropout of the fused tail (imdb-wiki-dir/resnet.py:98-101,146-147 = agedb-dir/resnet.py: nn.Dropout(p) applied to the
+ * calibrated encoding before the linear layer, training mode only).  The mask is Philox4x32-10 (Random123 constants) and a
+ * pure function of (seed, offset, p, e) for element e = b * C + c:
+ *   key = (seed & 0xffffffff, seed >> 32), counter = ((e >> 2) & 0xffffffff, (e >> 2) >> 32, offset & 0xffffffff, offset >> 32),
+ *   r = philox(counter, key)[e & 3], keep = r < min(floor((1 - p) * 2^32), 2^32 - 1)  (double),
+ *   drop(v) = keep ? v * (float)(1 / (1 - p)) : 0  (p == 1: everything dropped).  p outside [0, 1] -> DIR_EINVAL.
+ * It is not nn.Dropout's random stream.
+ * dir_tail_dropout_fwd: dir_tail_fwd with pred[b] = sum_c drop(encoding[b, c]) * weight[c] + bias; `encoding` is still the
+ *        calibrated, PRE-dropout tensor (what resnet.py returns and the FDS epoch statistics read, A.2).
+ * dir_tail_dropout_bwd: dir_tail_bwd with the mask regenerated from (seed, offset, p):
+ *        dx = ((keep ? dpred[b] * weight[c] * scale : 0) (+ dencoding[b, c])) * s[bin_b, c] / HW,
+ *        dweight[c] = sum_b dpred[b] * drop(encoding[b, c]) (same fixed order), dbias unchanged.  Pass the forward's seed / offset / p.
+ * dir_dropout_mask: keep [B, C] uint8 (0 / 1) of the same mask. */
+int dir_tail_dropout_fwd(const void* x, int dtype, const float* labels, const int32_t* bins_in, int B, int HW, int C,
+                         int bucket_start, int bucket_num, const float* m1, const float* scale, const float* m2,
+                         const float* weight, const float* bias, float* encoding, float* pred, int32_t* bins_out,
+                         uint64_t seed, uint64_t offset, double p, dir_stream_t stream);
+int dir_tail_dropout_bwd(const float* dpred, const float* dencoding, const int32_t* bins, const float* scale, const float* weight,
+                         const float* encoding, int B, int HW, int C, int dtype, void* dx, float* dweight, float* dbias,
+                         void* workspace, size_t workspace_bytes, uint64_t seed, uint64_t offset, double p, dir_stream_t stream);
+int dir_dropout_mask(uint64_t seed, uint64_t offset, double p, int B, int C, uint8_t* keep, dir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
