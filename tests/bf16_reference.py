@@ -11,6 +11,22 @@ Bars (``ratio`` = max |got - ref| / bar, a test passes at ratio <= 1):
     float32 sums: 2e-5 S of those sums, propagated);
   * float32 outputs of reductions: ``2e-5 S`` per element, S = sum of |terms| of that element's sum in float64;
   * float32 statistics (save_mean / save_rstd / running stats): ``1e-5 |ref| + 1e-6 max|ref|``.
+
+Convolutions (``conv_fwd_ref`` / ``conv_dgrad_ref`` / ``conv_wgrad_ref``: explicit per-tap GEMMs, each returning the result and S, the
+same operation on |operands|):
+  * bf16 output of one float32 sum (forward, plain data gradient): ``bf16_bar(ref, SUM_REL S)``. The MFMA kernels add exact products
+    into a float32 accumulator 16 at a time, so the longest chain of the network (K = 9 * 512 = 4608) has 288 roundings:
+    288 * 2^-24 S < 2e-5 S even in the worst case.
+  * bf16 output after fused roundings (``join_ref``): the kernel stores bf16(bf16(conv) + addend) and adds the compact stride-2 addend
+    with one more rounding. ref is the exact total; every intermediate rounding adds half an ulp of the intermediate,
+    ``2^-8 (|intermediate| + e)`` with e the error the intermediate already carries. The error e of the value before the final rounding
+    also moves that rounding's half ulp: all extra terms are scaled by (1 + 2^-8). Where the ReLU mask is 0 the output is exactly 0.
+  * float32 weight gradient: BOTH ``SUM_REL S`` (holds for any float32 order of an honest sum) and ``WGRAD_REL max|ref|`` per
+    element. S grows like sqrt(M) faster than |dW|: at M = 256 * 56^2 the median S / |ref| is ~825, so 2e-5 S alone allows ~1.6 % of
+    |ref| — a dropped 64-pixel K-step would pass. An honest split-K order reaches ~0.06 of the second bar there
+    (tests/test_bf16_reference_host.py emulates it).
+  * forward statistics (the epilogue's per-tile column sums of the stored y): ``stats_bar`` = 1e-5 |ref| + 1e-5 max|ref| against
+    float64 sums of the kernel's own y (test_hip_conv.py's tolerance).
 """
 import torch
 
@@ -20,6 +36,8 @@ SUM_REL = 2e-5                # float32 sum chains of a few hundred terms: n 2^-
 STAT_REL = 1e-5               # save_mean / save_rstd / running statistics
 TIE_REL = 4 * 2.0 ** -24      # two candidates within this of each other (relative) may be ordered either way in float32
 AMBIGUOUS_MAX = 1e-3          # kernel decisions taken as given must stay rarer than this
+WGRAD_REL = 1e-5              # float32 weight gradients: second bar, relative to the array's scale (test_hip_conv_wgrad3.py's)
+CONV_STATS_REL = 1e-5         # forward statistics column sums: relative to the element and to the array's scale
 
 
 # ---- bars -------------------------------------------------------------------------------------------------------------------
@@ -225,3 +243,133 @@ def stem_wgrad_ref(dy, x):
     dw = conv2d_weight(xd, shape, dyd, stride=2, padding=3)
     S = conv2d_weight(xd.abs(), shape, dyd.abs(), stride=2, padding=3)
     return dw, S
+
+
+# ---- convolutions (explicit per-tap GEMMs, NCHW in and out, float64; CPU or GPU) -------------------------------------------------
+def _out_hw(h, w, r, s, stride, pad):
+    return (h + 2 * pad - r) // stride + 1, (w + 2 * pad - s) // stride + 1
+
+
+def _tap(t, i, j, stride, ho, wo):
+    """Rows of padded t [N, C, Hp, Wp] that tap (i, j) reads for the output grid ho x wo: [N, C, ho, wo] view."""
+    return t[:, :, i:i + stride * (ho - 1) + 1:stride, j:j + stride * (wo - 1) + 1:stride]
+
+
+def _gemm(a, b):
+    """[N, C, H, W] x [C, D] -> [N, D, H, W] (channels-last GEMM)."""
+    return (a.permute(0, 2, 3, 1) @ b).permute(0, 3, 1, 2)
+
+
+def conv_fwd_ref(x, w, stride, pad):
+    """y[n, co, ho, wo] = sum over (ci, i, j) of x[n, ci, stride ho - pad + i, stride wo - pad + j] w[co, ci, i, j] (zero outside the map).
+    Returns (y, S) in float64, S = the same sum of |terms|."""
+    xd, wd = x.double(), w.double()
+    n, _, h, wdt = xd.shape
+    cout, _, r, s = wd.shape
+    ho, wo = _out_hw(h, wdt, r, s, stride, pad)
+    xp = torch.nn.functional.pad(xd, (pad, pad, pad, pad))
+    xa = xp.abs()
+    y = torch.zeros((n, cout, ho, wo), dtype=torch.float64, device=xd.device)
+    S = torch.zeros_like(y)
+    for i in range(r):
+        for j in range(s):
+            wt = wd[:, :, i, j].t()
+            y += _gemm(_tap(xp, i, j, stride, ho, wo), wt)
+            S += _gemm(_tap(xa, i, j, stride, ho, wo), wt.abs())
+    return y, S
+
+
+def conv_dgrad_ref(dy, w, x_shape, stride, pad):
+    """Gradient of conv(x, w, stride, pad) with respect to x for output gradient dy, from the ORIGINAL weight w [Cout, Cin, R, S]:
+    dx[n, ci, h, w] = sum over (co, i, j) with h = stride ho - pad + i, w = stride wo - pad + j of dy[n, co, ho, wo] w[co, ci, i, j].
+    Returns (dx, S) in float64."""
+    dyd, wd = dy.double(), w.double()
+    n, cin, h, wdt = x_shape
+    cout, _, r, s = wd.shape
+    ho, wo = dyd.shape[2], dyd.shape[3]
+    dxp = torch.zeros((n, cin, h + 2 * pad, wdt + 2 * pad), dtype=torch.float64, device=dyd.device)
+    Sp = torch.zeros_like(dxp)
+    da = dyd.abs()
+    for i in range(r):
+        for j in range(s):
+            wt = wd[:, :, i, j]
+            _tap(dxp, i, j, stride, ho, wo).add_(_gemm(dyd, wt))
+            _tap(Sp, i, j, stride, ho, wo).add_(_gemm(da, wt.abs()))
+    return dxp[:, :, pad:pad + h, pad:pad + wdt], Sp[:, :, pad:pad + h, pad:pad + wdt]
+
+
+def conv_wgrad_ref(dy, x, k, stride, pad):
+    """dW[co, ci, i, j] = sum over (n, ho, wo) of dy[n, co, ho, wo] x[n, ci, stride ho - pad + i, stride wo - pad + j] (k x k kernel).
+    Returns (dW, S) in float64."""
+    dyd, xd = dy.double(), x.double()
+    ho, wo = dyd.shape[2], dyd.shape[3]
+    cout, cin = dyd.shape[1], xd.shape[1]
+    xp = torch.nn.functional.pad(xd, (pad, pad, pad, pad))
+    g = dyd.permute(0, 2, 3, 1).reshape(-1, cout)
+    ga = g.abs()
+    dw = torch.zeros((cout, cin, k, k), dtype=torch.float64, device=dyd.device)
+    S = torch.zeros_like(dw)
+    for i in range(k):
+        for j in range(k):
+            xt = _tap(xp, i, j, stride, ho, wo).permute(0, 2, 3, 1).reshape(-1, cin)
+            dw[:, :, i, j] = g.t() @ xt
+            S[:, :, i, j] = ga.t() @ xt.abs()
+    return dw, S
+
+
+def up2(a, ho, wo):
+    """Compact stride-2 gradient [N, C, ho/2, wo/2] placed at the even pixels of an [N, C, ho, wo] map (zeros elsewhere)."""
+    out = torch.zeros((a.shape[0], a.shape[1], ho, wo), dtype=torch.float64, device=a.device)
+    out[:, :, 0::2, 0::2] = a.double()
+    return out
+
+
+def join_ref(conv, S, addend=None, addend_s2=None, mask=None):
+    """Fused data gradient relu'(mask) * (conv + addend + up2(addend_s2)) from the exact conv (and its S). The kernel rounds
+    bf16(conv), then bf16(. + addend), then (even pixels) bf16(. + compact): each rounding that is not the last is an intermediate.
+    Returns (ref, bar): bar = bf16_bar(ref, (1 + 2^-8) (SUM_REL S + sum of 2^-8 (|intermediate| + e))); mask 0 -> ref 0 (the test
+    asserts exact zeros there separately)."""
+    c = conv.double()
+    e = SUM_REL * S.double()
+    ho, wo = c.shape[2], c.shape[3]
+    total, extra = c, e
+    if addend is not None:
+        extra = extra + BF16_REL * (total.abs() + extra)                 # bf16(conv) before the add
+        total = total + addend.double()
+    if addend_s2 is not None:
+        even = torch.zeros_like(c, dtype=torch.bool)
+        even[:, :, 0::2, 0::2] = True
+        extra = torch.where(even, extra + BF16_REL * (total.abs() + extra), extra)   # the value before the compact add, rounded
+        total = total + up2(addend_s2, ho, wo)
+    if mask is not None:
+        keep = mask.bool()
+        total = torch.where(keep, total, torch.zeros((), dtype=torch.float64, device=c.device))
+        extra = torch.where(keep, extra, torch.zeros((), dtype=torch.float64, device=c.device))
+    return total, bf16_bar(total, (1.0 + BF16_REL) * extra)
+
+
+def bits_to_mask(bits, shape):
+    """Bit-per-element ReLU mask ([N*H*W*C / 8] bytes, NHWC element order, element e at bit e % 8 of byte e // 8) -> bool [N, C, H, W]."""
+    n, c, h, w = shape
+    b = bits.reshape(-1).long()
+    flat = ((b.unsqueeze(1) >> torch.arange(8, device=b.device)) & 1).reshape(-1).bool()
+    return flat.view(n, h, w, c).permute(0, 3, 1, 2)
+
+
+def mask_to_bits(mask, reverse=False):
+    """bool [N, C, H, W] -> uint8 bytes in the layout of bits_to_mask (reverse: the defect 'bit order reversed within a byte')."""
+    flat = mask.permute(0, 2, 3, 1).reshape(-1, 8).long()
+    sh = torch.arange(8, device=mask.device)
+    if reverse:
+        sh = 7 - sh
+    return (flat << sh).sum(1).to(torch.uint8)
+
+
+def wgrad_bar(ref, S):
+    """Both weight-gradient bars at once: min(SUM_REL S, WGRAD_REL max|ref|) per element."""
+    return torch.minimum(sum_bar(S), torch.full_like(S.double(), WGRAD_REL * float(ref.double().abs().max()) + 1e-30))
+
+
+def stats_bar(ref):
+    ref = ref.double()
+    return CONV_STATS_REL * ref.abs() + CONV_STATS_REL * float(ref.abs().max()) + 1e-30

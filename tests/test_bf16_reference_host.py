@@ -206,3 +206,180 @@ def test_relu_ambiguity_scales_with_the_terms():
     assert ok and frac == 0.5
     assert not R.relu_ambiguous(pre, torch.tensor([[[[False]], [[True]]]]))[1]      # without the terms: 1e-9 is not near 0
     assert not R.relu_ambiguous(pre, torch.tensor([[[[True]], [[False]]]]), terms)[1]
+
+
+# ---- convolutions ------------------------------------------------------------------------------------------------------------------
+CONV_CASES = [  # (N, Cin, H, W, Cout, k, stride, pad)
+    (2, 3, 5, 3, 4, 3, 1, 1), (2, 3, 5, 3, 4, 3, 2, 1), (1, 2, 6, 6, 3, 3, 2, 1), (2, 2, 7, 5, 3, 3, 2, 0),
+    (2, 4, 5, 3, 3, 1, 1, 0), (2, 4, 6, 4, 3, 1, 2, 0), (2, 4, 5, 5, 3, 1, 2, 0), (3, 2, 1, 1, 2, 1, 1, 0),
+    (3, 2, 1, 1, 2, 3, 1, 1), (2, 2, 2, 2, 3, 3, 1, 1), (2, 2, 2, 2, 3, 3, 2, 1), (1, 3, 2, 2, 2, 1, 2, 0),
+]
+
+
+@pytest.mark.parametrize("case", CONV_CASES)
+def test_conv_references_match_torch(case):
+    """conv_fwd_ref / conv_dgrad_ref / conv_wgrad_ref equal F.conv2d / conv2d_input / conv2d_weight in float64, and S bounds |result|."""
+    from torch.nn.grad import conv2d_input, conv2d_weight
+    n, cin, h, w, cout, k, stride, pad = case
+    g = _gen(sum(case))
+    x = torch.randn((n, cin, h, w), generator=g, dtype=torch.float64)
+    wt = torch.randn((cout, cin, k, k), generator=g, dtype=torch.float64)
+    y, S = R.conv_fwd_ref(x, wt, stride, pad)
+    ya = F.conv2d(x, wt, None, stride, pad)
+    torch.testing.assert_close(y, ya, rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(S, F.conv2d(x.abs(), wt.abs(), None, stride, pad), rtol=1e-12, atol=1e-12)
+    dy = torch.randn(ya.shape, generator=g, dtype=torch.float64)
+    dx, Sx = R.conv_dgrad_ref(dy, wt, x.shape, stride, pad)
+    torch.testing.assert_close(dx, conv2d_input(x.shape, wt, dy, stride, pad), rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(Sx, conv2d_input(x.shape, wt.abs(), dy.abs(), stride, pad), rtol=1e-12, atol=1e-12)
+    dw, Sw = R.conv_wgrad_ref(dy, x, k, stride, pad)
+    torch.testing.assert_close(dw, conv2d_weight(x, wt.shape, dy, stride, pad), rtol=1e-12, atol=1e-12)
+    torch.testing.assert_close(Sw, conv2d_weight(x.abs(), wt.shape, dy.abs(), stride, pad), rtol=1e-12, atol=1e-12)
+    for r, s in ((y, S), (dx, Sx), (dw, Sw)):
+        assert (s >= r.abs() - 1e-12).all()
+
+
+def test_join_reference_and_bit_masks():
+    """join_ref = mask * (conv + addend + up2(compact)); the bit layout round-trips and its reversed order differs."""
+    g = _gen(21)
+    shape = (2, 16, 6, 4)
+    c = torch.randn(shape, generator=g, dtype=torch.float64)
+    a = torch.randn(shape, generator=g, dtype=torch.float64)
+    a2 = torch.randn((2, 16, 3, 2), generator=g, dtype=torch.float64)
+    m = torch.rand(shape, generator=g) > 0.4
+    ref, bar = R.join_ref(c, c.abs(), a, a2, m)
+    up = torch.zeros(shape, dtype=torch.float64)
+    up[:, :, 0::2, 0::2] = a2
+    torch.testing.assert_close(ref, torch.where(m, c + a + up, torch.zeros_like(c)), rtol=0, atol=0)
+    assert (bar > 0).all()
+    assert torch.equal(R.bits_to_mask(R.mask_to_bits(m), shape), m)
+    assert not torch.equal(R.bits_to_mask(R.mask_to_bits(m, reverse=True), shape), m)
+
+
+# An honest float32 kernel, emulated: exact bf16 x bf16 products summed 16 at a time (one MFMA step), each group added to a float32
+# accumulator with one rounding; split-K ranges accumulated from zero and their partials summed in split order in float32.
+def _emulate(a, b, splits=1, round_kstep=False, chunk=16):
+    """a, b: [E, K] float64 holding bf16 values. Returns float32 results [E] as float64. round_kstep: the defect 'running sum rounded
+    to bf16 once per 64-wide K-step'."""
+    e, k = a.shape
+    groups = (a * b).view(e, k // chunk, chunk).sum(-1)
+    nch = groups.shape[1]
+    per = -(-nch // splits)
+    groups = torch.nn.functional.pad(groups, (0, per * splits - nch)).view(e, splits, per)
+    acc = torch.zeros((e, splits), dtype=torch.float32)
+    for i in range(per):
+        acc = (acc.double() + groups[:, :, i]).float()
+        if round_kstep and (i + 1) % (64 // chunk) == 0:
+            acc = acc.bfloat16().float()
+    out = acc[:, 0]
+    for s in range(1, splits):
+        out = (out.double() + acc[:, s].double()).float()
+    return out.double()
+
+
+def _operands(e, k, seed, one_signed):
+    g = _gen(seed)
+    a = torch.randn((e, k), generator=g)
+    if one_signed:
+        a = torch.relu(a) + 0.01                               # post-ReLU activations: one-signed x
+    b = torch.randn((e, k), generator=g) * (2.0 / k) ** 0.5
+    return a.bfloat16().double(), b.bfloat16().double()
+
+
+@pytest.mark.parametrize("k", [576, 4608])
+@pytest.mark.parametrize("one_signed", [False, True])
+def test_conv_forward_bar_is_sound_and_has_teeth(k, one_signed):
+    """bf16 output of one float32 sum: bf16_bar(ref, SUM_REL S) passes the emulated honest kernel (RNE output) at the longest K of the
+    network and rejects truncation, per-K-step bf16 rounding of the running sum and a missing 64-channel K block."""
+    a, b = _operands(8192, k, k + int(one_signed), one_signed)
+    ref = (a * b).sum(1)
+    S = (a * b).abs().sum(1)
+    bar = R.bf16_bar(ref, R.SUM_REL * S)
+    acc = _emulate(a, b)
+    honest = R.ratio(acc.bfloat16().double(), ref, bar)
+    assert honest <= 1.0, f"honest kernel: ratio {honest:.3g}"
+    trunc = R.has_teeth(R.bf16_round_toward_zero(acc), ref, bar, "rounded toward zero")
+    kstep = R.has_teeth(_emulate(a, b, round_kstep=True).bfloat16().double(), ref, bar, "running sum rounded per K-step")
+    a2 = a.clone()
+    a2[:, 64:128] = 0
+    block = R.has_teeth(_emulate(a2, b).bfloat16().double(), ref, bar, "missing 64-channel K block")
+    print(f"K={k} one_signed={one_signed}: honest {honest:.3g}, truncation {trunc:.3g}, per-K-step bf16 {kstep:.3g}, "
+          f"missing block {block:.3g}")
+
+
+def test_conv_border_tap_bar_has_teeth():
+    """A data path that reads the last input row / column as padding (a missing border tap) is rejected by the forward bar."""
+    g = _gen(23)
+    x = torch.randn((2, 64, 7, 7), generator=g).bfloat16().double()
+    w = (torch.randn((64, 64, 3, 3), generator=g) * (2.0 / 576) ** 0.5).bfloat16().double()
+    ref, S = R.conv_fwd_ref(x, w, 1, 1)
+    bar = R.bf16_bar(ref, R.SUM_REL * S)
+    assert R.ratio(ref.float().bfloat16().double(), ref, bar) <= 1.0
+    x2 = x.clone()
+    x2[:, :, -1, :] = 0
+    x2[:, :, :, -1] = 0
+    r = R.has_teeth(R.conv_fwd_ref(x2, w, 1, 1)[0].float().bfloat16().double(), ref, bar, "missing border tap")
+    print(f"border tap: {r:.3g}")
+
+
+def test_join_bar_is_sound_and_has_teeth():
+    """bf16(bf16(bf16(conv) + addend) + compact) under a mask passes join_ref's bar; the compact addend added at odd pixels, a bit
+    mask read in reversed bit order, and truncated roundings are rejected."""
+    g = _gen(24)
+    shape = (4, 64, 8, 6)
+    dy = torch.randn(shape, generator=g).bfloat16().double()
+    w = (torch.randn((64, 64, 3, 3), generator=g) * (2.0 / 576) ** 0.5).bfloat16().double()
+    conv, S = R.conv_dgrad_ref(dy, w, shape, 1, 1)
+    add = torch.randn(shape, generator=g).bfloat16().double()
+    a2 = torch.randn((4, 64, 4, 3), generator=g).bfloat16().double()
+    mask = torch.rand(shape, generator=g) > 0.5
+    up = R.up2(a2, 8, 6)
+
+    def kernel(c32, rnd):
+        v = rnd(c32)
+        v = rnd(v + add)
+        v = torch.where(up != 0, rnd(v + up), v)
+        return torch.where(mask, v, torch.zeros_like(v))
+    rne = lambda t: t.float().bfloat16().double()               # noqa: E731
+    ref, bar = R.join_ref(conv, S, add, a2, mask)
+    honest = R.ratio(kernel(conv.float().double(), rne), ref, bar)
+    assert honest <= 1.0, honest
+    assert torch.equal(kernel(conv.float().double(), rne)[~mask], torch.zeros(int((~mask).sum()), dtype=torch.float64))
+    odd = torch.zeros_like(up)
+    odd[:, :, 1::2, 1::2] = a2
+    bad = rne(rne(conv) + add) + odd
+    R.has_teeth(torch.where(mask, rne(bad), torch.zeros_like(bad)), ref, bar, "compact addend at odd pixels")
+    rev = R.bits_to_mask(R.mask_to_bits(mask, reverse=True), shape)
+    v = kernel(conv.float().double(), rne)
+    R.has_teeth(torch.where(rev, rne(rne(rne(conv) + add) + up), torch.zeros_like(v)), ref, bar, "bit order reversed in a mask byte")
+    R.has_teeth(kernel(conv.float().double(), R.bf16_round_toward_zero), ref, bar, "join rounded toward zero")
+    print(f"join: honest {honest:.3g}")
+
+
+@pytest.mark.parametrize("one_signed", [False, True])
+def test_wgrad_bars_are_sound_and_have_teeth(one_signed):
+    """float32 dW at M = 256 * 56^2: the emulated honest split-K kernel passes both bars; a dW missing one 64-pixel K-step or one
+    split, or with co and ci transposed, is rejected — the first only thanks to the WGRAD_REL max|ref| bar."""
+    m, co, ci, splits = 256 * 56 * 56, 4, 4, 16
+    g = _gen(25 + int(one_signed))
+    dy = torch.randn((m, co), generator=g).bfloat16().double()
+    x = torch.randn((m, ci), generator=g)
+    if one_signed:
+        x = torch.relu(x)
+    x = x.bfloat16().double()
+    a = dy.t().repeat_interleave(ci, 0)                        # element (o, i): dy[:, o] . x[:, i]
+    b = x.t().repeat(co, 1)
+    ref = (a * b).sum(1)
+    S = (a * b).abs().sum(1)
+    bar = R.wgrad_bar(ref, S)
+    got = _emulate(a, b, splits=splits)
+    r_sum = R.ratio(got, ref, R.sum_bar(S))
+    r_max = R.ratio(got, ref, torch.full_like(ref, R.WGRAD_REL * float(ref.abs().max())))
+    assert r_sum <= 1.0 and r_max <= 1.0, f"honest split-K: {r_sum:.3g} of SUM_REL S, {r_max:.3g} of WGRAD_REL max|ref|"
+    step = (a[:, 64:128] * b[:, 64:128]).sum(1)
+    r_step = R.has_teeth(ref - step, ref, bar, "dW missing one 64-pixel K-step")
+    per = -(-m // splits)
+    r_split = R.has_teeth(ref - (a[:, :per] * b[:, :per]).sum(1), ref, bar, "dW missing one split")
+    r_tr = R.has_teeth(ref.view(co, ci).t().reshape(-1), ref, bar, "dW with co and ci transposed")
+    print(f"wgrad one_signed={one_signed}: honest {r_sum:.3g} (S bar) {r_max:.3g} (max bar); K-step {r_step:.3g}, split {r_split:.3g}, "
+          f"transposed {r_tr:.3g}, S-bar-only on the K-step {R.ratio(ref - step, ref, R.sum_bar(S)):.3g}")

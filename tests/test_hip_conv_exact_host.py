@@ -1,0 +1,34 @@
+"""CPU: the launch sites of the four bf16 convolution launchers are the ones test_hip_conv_exact.EXPECTED_KERNELS was written for. A new
+launch site (a hipLaunchKernelGGL, or a CV_LAUNCH / CP_LAUNCH / wg_launch / w3_launch instantiation) fails here until the list and the
+GPU matrix that must reach it are updated."""
+import os
+import re
+
+import pytest
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "imbalanced-regression_amd", "csrc")
+SITE = re.compile(r"hipLaunchKernelGGL\(|CV_LAUNCH\(\d|CP_LAUNCH\(\d|wg_launch<\d|w3_launch<\d")
+
+# file -> launch sites when the list was written. dir_conv.hip: 9 conv sites + 6 patch (CP_LAUNCH) + 6 register-staged (CV_LAUNCH)
+# instantiations + 4 optimizer / weight-preparation kernels; dir_conv_wgrad.hip: 2 generic + 4 wg_launch tiles + 2 DMA + 3 reductions;
+# dir_conv_wgrad3.hip: 1 + 4 w3_launch widths; dir_stem.hip: weight packing, forward, and the stem weight gradient's 2.
+SITES = {"dir_conv.hip": 25, "dir_conv_wgrad.hip": 11, "dir_conv_wgrad3.hip": 5, "dir_stem.hip": 4}
+
+
+@pytest.mark.parametrize("name", sorted(SITES))
+def test_conv_launch_sites_match_the_checked_list(name):
+    with open(os.path.join(CSRC, name)) as f:
+        n = len(SITE.findall(f.read()))
+    assert n == SITES[name], f"{name}: {n} launch sites, the list in tests/test_hip_conv_exact.py was written for {SITES[name]}"
+
+
+def test_expected_kernel_names_parse():
+    """The profiler-name canonicalisation reads demangled and mangled names alike."""
+    import test_hip_conv_exact as T
+    assert T._canon("void (anonymous namespace)::conv_igemm_kernel<128, 2, 2, false>((anonymous namespace)::ConvP)") == \
+        "conv_igemm_kernel<128,2,2,0>"
+    assert T._canon("_ZN12_GLOBAL__N_117conv_igemm_kernelILi128ELi2ELi2ELb0EEEvNS_5ConvPE") == "conv_igemm_kernel<128,2,2,0>"
+    assert T._canon("void (anonymous namespace)::conv_wgrad_reduce_kernel(float const*, int, unsigned long, float*)") == \
+        "conv_wgrad_reduce_kernel"
+    assert T._canon("conv_f32_wgrad_kernel<64>") is None and T._canon("stem_wgrad_kernel") is None
+    assert len(T.EXPECTED_KERNELS) == 36
