@@ -226,6 +226,47 @@ def scale_by_device_scalar(t, scalar):
     return out
 
 
+# ---- NYUD2-DIR evaluation -------------------------------------------------------------------------
+_EVAL_WS = {}
+
+
+def depth_eval_accumulate(pred, depth, mask, table, mult=10.0):
+    """pred [N, h, w] f32, depth [N, H, W] f32, mask [N, H, W] uint8 / bool or None, table [bucket_num, 8] f64 (accumulated into).
+    One fused pass (bilinear align-corners upsampling of ``pred`` in registers when the sizes differ); enqueue only, no sync.
+    The workspace is kept per (device, stream) and grown on demand: reuse is ordered by the stream."""
+    pred = L.require_device_tensor(pred, f32, "pred")
+    depth = L.require_device_tensor(depth, f32, "depth")
+    table = L.require_device_tensor(table, f64, "table")
+    if pred.dim() != 3 or depth.dim() != 3 or pred.shape[0] != depth.shape[0]:
+        raise ValueError(f"pred / depth must be [N, h, w] / [N, H, W], got {tuple(pred.shape)} / {tuple(depth.shape)}")
+    if table.dim() != 2 or table.shape[1] != 8:
+        raise ValueError("table must be [bucket_num, 8]")
+    dev = depth.device
+    if pred.device != dev or table.device != dev:
+        raise ValueError("pred, depth and table must live on one device")
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)                       # same bytes, no kernel
+        mask = L.require_device_tensor(mask, torch.uint8, "mask")
+        if mask.shape != depth.shape or mask.device != dev:
+            raise ValueError("mask must have depth's shape and device")
+    n, h, w = pred.shape
+    _, H, W = depth.shape
+    nb = table.shape[0]
+    per = max(1, 2_000_000_000 // max(H * W, h * w))            # the C-ABI indexes pixels with 32 bits: split very large batches
+    for a in range(0, n, per):
+        k = min(per, n - a)
+        nbytes = L.lib().dir_depth_eval_workspace(k * H * W, nb)
+        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+        ws = _EVAL_WS.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = _EVAL_WS[key] = _ws(nbytes, dev)
+        L.check(L.lib().dir_depth_eval_accumulate(L.ptr(pred[a:a + k]), L.ptr(depth[a:a + k]), L.ptr(mask[a:a + k]) if mask is not None else None,
+                                                  k, h, w, H, W, float(mult), nb, L.ptr(table), L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
+                "dir_depth_eval_accumulate")
+    return table
+
+
 # ---- K8 (host) ------------------------------------------------------------------------------------
 def lds_weights(labels, max_target, reweight, lds, window):
     """labels: any 1-D array-like (host). Returns np.float32 [n]."""

@@ -640,6 +640,26 @@ int dir_tail_dropout_bwd(const float* dpred, const float* dencoding, const int32
                          void* workspace, size_t workspace_bytes, uint64_t seed, uint64_t offset, double p, dir_stream_t stream);
 int dir_dropout_mask(uint64_t seed, uint64_t offset, double p, int B, int C, uint8_t* keep, dir_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * NYUD2-DIR balanced depth evaluation (nyud2-dir/util.py:35-133 `Evaluator`, nyud2-dir/test.py:39-59) in one streaming pass.
+ *   pred [N, h, w] f32 (the network output), depth [N, H, W] f32, mask [N, H, W] uint8 (non-zero = keep; NULL = every pixel).
+ *   (h, w) != (H, W): the prediction is upsampled bilinearly with align_corners=True at every target pixel, in registers
+ *   (float32 steps: s = i * ((in - 1) / (out - 1)), i0 = min(int(s), in - 1), l = s - i0, value = hy * (hx * v00 + lx * v01) +
+ *   ly * (hx * v10 + lx * v11)); the upsampled map is never written.  A pixel whose depth is NaN is skipped.
+ *   Per kept pixel, float32, one rounding per operation: bucket = min(int(depth * mult), bucket_num - 1) (depth <= 0 -> 0),
+ *   d = |pred - depth|, r = pred / depth unless that is < depth / pred (a NaN ratio stays NaN); the bucket's row of
+ *   table [bucket_num][8] f64 gains  d*d, d, d / depth, |log(pred) / ln10 - log(depth) / ln10|, [r <= 1.25], [r <= 1.5625],
+ *   [r <= 1.953125], 1.  Non-positive predictions put the reference's NaN / inf into the LG10 column; nothing is clamped.
+ *   `table` is ACCUMULATED INTO (zero it before the first call).  Sums are float64 in a fixed order (wavefront butterfly per bucket,
+ *   wave-private LDS rows, one partial per workgroup in `workspace`, partials folded in workgroup order by a second launch): the
+ *   result is bit-reproducible; no float atomics.  No host synchronisation.
+ *   workspace >= dir_depth_eval_workspace(N * H * W, bucket_num) bytes, 8-byte aligned.
+ *   DIR_EUNSUPPORTED: bucket_num > 256 (LDS layout), or N * H * W or N * h * w > 2.1e9 (32-bit pixel indices; split the batch). */
+size_t dir_depth_eval_workspace(long long n, int bucket_num);
+int dir_depth_eval_accumulate(const float* pred, const float* depth, const uint8_t* mask, int N, int h, int w, int H, int W,
+                              float mult, int bucket_num, double* table, void* workspace, size_t workspace_bytes,
+                              dir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
