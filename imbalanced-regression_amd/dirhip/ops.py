@@ -267,6 +267,38 @@ def depth_eval_accumulate(pred, depth, mask, table, mult=10.0):
     return table
 
 
+# ---- age evaluation (imdb-wiki-dir / agedb-dir validate) --------------------------------------------------------------------------
+def age_eval_accumulate(pred, label, valid, table):
+    """pred / label f32 of equal element count (any shape, e.g. [B] or [B, 1]), valid uint8 / bool of that count or None,
+    table [num_labels + 1, 5] f64 (accumulated into: sum e^2, sum e, sum ln e over e > 0, count of e == 0, NUM per integer label,
+    last row = every other label). One pass; enqueue only, no sync. Workspace as for ``depth_eval_accumulate``."""
+    pred = L.require_device_tensor(pred, f32, "pred")
+    label = L.require_device_tensor(label, f32, "label")
+    table = L.require_device_tensor(table, f64, "table")
+    if pred.numel() != label.numel():
+        raise ValueError(f"pred and label differ in size: {pred.numel()} vs {label.numel()}")
+    if table.dim() != 2 or table.shape[1] != 5 or table.shape[0] < 2:
+        raise ValueError("table must be [num_labels + 1, 5]")
+    dev = label.device
+    if pred.device != dev or table.device != dev:
+        raise ValueError("pred, label and table must live on one device")
+    if valid is not None:
+        if isinstance(valid, torch.Tensor) and valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)                     # same bytes, no kernel
+        valid = L.require_device_tensor(valid, torch.uint8, "valid")
+        if valid.numel() != label.numel() or valid.device != dev:
+            raise ValueError("valid must have label's element count and device")
+    n, num_labels = label.numel(), table.shape[0] - 1
+    nbytes = L.lib().dir_age_eval_workspace(n, num_labels)
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _EVAL_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _EVAL_WS[key] = _ws(nbytes, dev)
+    L.check(L.lib().dir_age_eval_accumulate(L.ptr(pred), L.ptr(label), L.ptr(valid), n, num_labels, L.ptr(table), L.ptr(ws), ws.numel(),
+                                            L.stream_ptr(dev)), "dir_age_eval_accumulate")
+    return table
+
+
 # ---- K8 (host) ------------------------------------------------------------------------------------
 def lds_weights(labels, max_target, reweight, lds, window):
     """labels: any 1-D array-like (host). Returns np.float32 [n]."""

@@ -10,7 +10,8 @@ Differences from the reference, all on purpose:
   * the hot loop and the FDS epoch tail come from ``dirhip.train_loop`` (device-resident features, loss read
     back every ``print_freq`` steps instead of every step);
   * extra, optional flags: ``--synthetic N`` (random images, no files needed), ``--amp {bf16,fp32,fp32x3,fp32x2}``, ``--amp_early``,
-    ``--max_steps`` (truncate epochs for smoke runs). ``tensorboard_logger`` is used when importable.
+    ``--max_steps`` (truncate epochs for smoke runs), ``--device_eval`` (validation / test metrics summed on the GPU by
+    ``dirhip.eval_age.ShotEvaluator`` and, under ``torchrun``, sharded over the ranks). ``tensorboard_logger`` is used when importable.
 """
 import argparse
 import logging
@@ -102,6 +103,10 @@ def build_parser(dataset_default='imdb_wiki'):
                    'of the training set over the ranks is then FIXED for the whole run (every rank caches its own shard; batches never mix samples of '
                    'different shards and a rank\'s BatchNorm statistics always see the same subset) — unlike the default path, which redraws the partition '
                    'every epoch like a DistributedSampler; every rank allocates the full-size cache')
+    p.add_argument('--device_eval', action='store_true', default=False, help='validate / test with dirhip.eval_age.ShotEvaluator: per-label error sums '
+                   'in a float64 table on the GPU (dir_age_eval_accumulate), one read-back per pass instead of every prediction; with more than one '
+                   'rank each rank evaluates its shard of the set and the tables are summed, so every rank reports the same numbers. Sums are '
+                   'float64 and the overall MSE / L1 are sum / NUM: equal to the default path to float32 rounding, not bit for bit')
     p.add_argument('--overwrite', action='store_true', help='delete an existing run folder of the same name (the reference asks on '
                    'the terminal; without a terminal nothing is deleted unless this flag is given)')
     p.set_defaults(augment=True)
@@ -225,10 +230,44 @@ def train(train_batches, n_steps, model, optimizer, epoch, args, store):
     return losses.avg
 
 
-def validate(val_batches, n_batches, model, args, train_labels=None, prefix='Val'):
+def eval_shard(n, rank, world, device_eval):
+    """Which samples of an n-sample validation / test set this rank evaluates: ``(indices, valid)``. Without ``--device_eval``, or with
+    one rank, the whole set (``valid`` None). With it, this rank's shard of ``parallel.shard_indices`` in dataset order; ``valid`` is
+    False at the wrap-around rows that pad the shard, which ``ShotEvaluator.update`` then skips."""
+    if not device_eval or world == 1:
+        return torch.arange(n), None
+    return shard_indices(n, rank, world, with_valid=True)
+
+
+def validate_device(val_batches, model, train_labels, prefix='Val', evaluator=None):
+    """``validate`` with ``--device_eval``: every batch is one ``ShotEvaluator.update`` (enqueue only; a fourth batch item is the
+    shard's padding mask), the tables of the ranks are summed, and the per-label sums are read back once."""
+    from .eval_age import ShotEvaluator
+    ev = ShotEvaluator(train_labels) if evaluator is None else evaluator
+    ev.reset()
+    model.eval()
+    with torch.no_grad():
+        for batch in val_batches():
+            outputs = model(batch[0]).float()
+            valid = batch[3] if len(batch) > 3 else None
+            if valid is not None:
+                valid = torch.as_tensor(valid, dtype=torch.bool).to(outputs.device, non_blocking=True)
+            ev.update(outputs, batch[1], valid)
+    ev.merge_across_ranks()
+    res = ev.results()
+    o = res['overall']
+    print(f" * Overall: MSE {o['mse']:.3f}\tL1 {o['l1']:.3f}\tG-Mean {o['gmean']:.3f}")
+    for shot, title in (('many', 'Many'), ('median', 'Median'), ('low', 'Low')):
+        print(f" * {title}: MSE {res[shot]['mse']:.3f}\tL1 {res[shot]['l1']:.3f}\tG-Mean {res[shot]['gmean']:.3f}")
+    return o['mse'], o['l1'], o['gmean']
+
+
+def validate(val_batches, n_batches, model, args, train_labels=None, prefix='Val', evaluator=None):
     """train.py:286-335. Same numbers as the reference: per-batch float32 MSE / L1 means averaged with the batch sizes as
     weights (``AverageMeter``), G-Mean of all absolute errors, per-shot metrics — but the per-batch values are read back
-    once at the end instead of with two ``.item()`` host syncs per batch."""
+    once at the end instead of with two ``.item()`` host syncs per batch. With ``args.device_eval``: ``validate_device``."""
+    if getattr(args, 'device_eval', False):
+        return validate_device(val_batches, model, train_labels, prefix, evaluator)
     losses_mse = AverageMeter('Loss (MSE)', ':.3f')
     losses_l1 = AverageMeter('Loss (L1)', ':.3f')
     progress = ProgressMeter(n_batches, [losses_mse, losses_l1], prefix=f'{prefix}: ')
@@ -328,7 +367,8 @@ def run(argv=None, dataset_default='imdb_wiki'):
             return lambda: train_set.device_batches(idx, args.batch_size, device, seed=epoch, valid=valid)
 
         def eval_batches(ds):
-            return lambda: ds.device_batches(torch.arange(len(ds)), args.batch_size, device)
+            idx, valid = eval_shard(len(ds), rank, world, args.device_eval)
+            return lambda: ds.device_batches(idx, args.batch_size, device, valid=valid)
         steps_per_epoch = (len(shard_indices(n_train, rank, world)) + args.batch_size - 1) // args.batch_size
         n_val = (len(val_set) + args.batch_size - 1) // args.batch_size
     else:
@@ -380,6 +420,9 @@ def run(argv=None, dataset_default='imdb_wiki'):
             return batches
 
         def eval_batches(ds):
+            idx, valid = eval_shard(len(ds), rank, world, args.device_eval)
+            if valid is not None:
+                ds = _ShardSubset(ds, idx.tolist(), valid.tolist())
             loader = DataLoader(ds, batch_size=args.batch_size, shuffle=False, **loader_kw)
             return lambda: _loader_batches(loader, device, aug_eval, dev_resize)
         steps_per_epoch = (len(shard_indices(n_train, rank, world)) + args.batch_size - 1) // args.batch_size

@@ -3,7 +3,9 @@
  *
  * The reference has no FFI (it is 100 % Python); its boundary is the Python module
  * surface fds.py / loss.py / utils.py / datasets.py. Each entry point below names the reference
- * lines whose device work it replaces. Conventions:
+ * lines whose device work it replaces. The last two sections are the evaluators: NYUD2-DIR's balanced depth
+ * metrics and the balanced age metrics of train.py's validate / shot_metrics, each as sums in a float64 table.
+ * Conventions:
  *   - extern "C", plain pointers and sizes; no torch types.
  *   - every pointer is a DEVICE pointer owned by the caller unless the comment says "host";
  *     nothing is allocated inside; scratch comes from a caller-provided workspace.
@@ -659,6 +661,23 @@ size_t dir_depth_eval_workspace(long long n, int bucket_num);
 int dir_depth_eval_accumulate(const float* pred, const float* depth, const uint8_t* mask, int N, int h, int w, int H, int W,
                               float mult, int bucket_num, double* table, void* workspace, size_t workspace_bytes,
                               dir_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Balanced age evaluation (imdb-wiki-dir/train.py:286-391 `validate` + `shot_metrics`) in one streaming pass per batch.
+ *   pred [n] f32 (the network output), label [n] f32, valid [n] uint8 (non-zero = keep; NULL = every sample).
+ *   Row of a sample: (int)label when label is integral and 0 <= label < num_labels; every other label (fractional, negative,
+ *   NaN, >= num_labels) goes to row num_labels.  Per kept sample, e = |pred - label| and e * e in float32 (one rounding per
+ *   operation, as the reference's `np.abs(preds - labels)`); the row of table [num_labels + 1][5] f64 gains
+ *   e * e,  e,  log((double)e) if e > 0,  [e == 0],  1.
+ *   `table` is ACCUMULATED INTO (zero it before the first call).  Sums are float64 in a fixed order (samples of a wavefront one
+ *   after the other, in lane order, into wave-private LDS rows, the four wave tables in wave order, one partial per workgroup in `workspace`,
+ *   partials folded in workgroup order by a second launch): bit-reproducible; no float atomics.  No host synchronisation.
+ *   Any n >= 0; n == 0 returns DIR_OK without touching a pointer.
+ *   workspace >= dir_age_eval_workspace(n, num_labels) bytes, 8-byte aligned.
+ *   DIR_EUNSUPPORTED: num_labels + 1 > 256 (LDS layout). */
+size_t dir_age_eval_workspace(long long n, int num_labels);
+int dir_age_eval_accumulate(const float* pred, const float* label, const uint8_t* valid, long long n, int num_labels,
+                            double* table, void* workspace, size_t workspace_bytes, dir_stream_t stream);
 
 #ifdef __cplusplus
 }
