@@ -22,6 +22,11 @@
 // All LDS offsets are computed once and pinned in registers, the LDS stage is a template literal: a K-step is 16 MFMAs,
 // 24 LDS and 8 buffer instructions and ~16 VALU instructions.
 // Workgroup ids are remapped so that the N-tiles of one M-tile run on the same XCD (A tile re-reads hit that L2).
+//
+// This file: the four forward / data-gradient kernels (register-staged, LDS-DMA, 256 x 256 CU tile, patch-staged 3x3), the kernel
+// selection (conv_plan) and the exported dir_conv_* launch entry points. Shared device pieces: dir_conv_index.h (tile remap, pixel
+// decode), dir_conv_shared.h (parameters, A-row origin, staging), dir_conv_epilogue.h (store loop). Weight gradients:
+// dir_conv_wgrad*.hip; optimizer steps and bf16 weight preparation: dir_optim.hip.
 #include <cstdlib>
 #include <type_traits>
 #include "dir_common.h"
@@ -49,14 +54,8 @@ conv_igemm_kernel(ConvP p) {
     unsigned char* As = smem;
     unsigned char* Bs = smem + NBUF * A_BYTES;
 
-    // ---- workgroup -> (m tile, n tile), XCD-aware and bijective: the hardware deals workgroup b to XCD b % 8, so the
-    // linear tile space is cut into 8 contiguous chunks and the N-tiles of one M-tile run on the same XCD (the A-tile
-    // re-reads hit that L2)
-    int lin;
-    {
-        const int b = blockIdx.x, q = p.nblocks / 8, r = p.nblocks % 8, xcd = b % 8, i = b / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    // ---- workgroup -> (m tile, n tile): the N-tiles of one M-tile run on the same XCD (the A-tile re-reads hit that L2)
+    const int lin = cv_xcd_tile(blockIdx.x, p.nblocks);
     const int mt = lin / p.ntn, nt = lin - mt * p.ntn;
     const int m0 = mt * CV_BM, n0 = nt * BN;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -64,39 +63,17 @@ conv_igemm_kernel(ConvP p) {
     const int wn = (BN == 128) ? (wave & 1) : 0;
     const int frow = lane & 31, fhalf = lane >> 5;
 
-    // ---- loader coordinates: thread loads the 16-B chunk (t & 7) of rows (t >> 3) + 32 i.
-    // Everything position dependent is computed ONCE: per row the signed byte offset of its (hi0, wi0) pixel and a bit
-    // mask of the filter taps that fall inside the image; per K-step a wave-uniform offset is added and out-of-image
-    // taps are sent out of the buffer's range (the buffer load then returns zeros: no masking instructions).
+    // ---- loader coordinates: thread loads the 16-B chunk (t & 7) of rows (t >> 3) + 32 i (row origin and tap mask: cv_row_origin)
     const int lrow = t >> 3, lchunk = t & 7;
     int aoff[4];
     uint32_t amask[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = m0 + lrow + 32 * i;
-        aoff[i] = 0; amask[i] = 0;
-        if (m < p.M) {
-            if (p.simple) { aoff[i] = (m * p.Cin + lchunk * 8) * 2; amask[i] = 1u; continue; }
-            // (n, ho, wo) from m: float reciprocal + one correction step instead of integer divisions (exact for m < 2^24)
-            int q1 = (int)((float)m * p.inv_wo), wo = m - q1 * p.Wo;
-            if (wo < 0) { --q1; wo += p.Wo; } else if (wo >= p.Wo) { ++q1; wo -= p.Wo; }
-            int n = (int)((float)q1 * p.inv_ho), ho = q1 - n * p.Ho;
-            if (ho < 0) { --n; ho += p.Ho; } else if (ho >= p.Ho) { ++n; ho -= p.Ho; }
-            const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
-            aoff[i] = (((n * p.H + hi0) * p.W + wi0) * p.Cin + lchunk * 8) * 2;
-            for (int r = 0; r < p.R; ++r)
-                for (int s2 = 0; s2 < p.S; ++s2)
-                    if ((unsigned)(hi0 + r) < (unsigned)p.H && (unsigned)(wi0 + s2) < (unsigned)p.W) amask[i] |= 1u << (r * p.S + s2);
-        }
-    }
+    for (int i = 0; i < 4; ++i) cv_row_origin(p, m0 + lrow + 32 * i, lchunk, aoff[i], amask[i]);
     const int K = p.KT * CV_BK;
     int woff[BROWS];                                       // byte offset of this thread's chunk in weight row n0 + lrow + 32 i
 #pragma unroll
     for (int i = 0; i < BROWS; ++i) woff[i] = ((n0 + lrow + 32 * i) * K + lchunk * 8) * 2;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), (short)0,
-                                                                           (int)((unsigned)(p.N * p.H * p.W) * (unsigned)p.Cin * 2u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w), (short)0,
-                                                                           (int)((unsigned)p.Cout * (unsigned)K * 2u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = cv_rsrc_x(p), rs_w = cv_rsrc_w(p, K);
     // LDS byte offsets, pinned in registers: one for the loader's stores (rows + 32 i are immediates; the swizzle of
     // row lrow + 32 i equals that of lrow) and one per fragment read of a K-step
     uint32_t st_off = lrow * CV_ROWB + ((lchunk ^ ((lrow >> 1) & 7)) << 4);
@@ -151,12 +128,7 @@ conv_igemm_kernel(ConvP p) {
     }
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.0f;
+    cv_zero_acc(acc);
 
     // one K-step of MFMAs on LDS stage `buf` (a literal: the stage folds into the instructions' immediate offsets):
     // 4 x (4 fragment reads, 4 (or 2) MFMA 32x32x16)
@@ -274,11 +246,7 @@ conv_igemm_dma_kernel(ConvP p) {
     constexpr int MI = (BN == 128) ? 2 : 1;
     constexpr int NI = 2;
     constexpr int WM = MI * 32;
-    int lin;
-    {
-        const int b = blockIdx.x, q = p.nblocks / 8, r = p.nblocks % 8, xcd = b % 8, i = b / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    const int lin = cv_xcd_tile(blockIdx.x, p.nblocks);
     const int mt = lin / p.ntn, nt = lin - mt * p.ntn;
     const int m0 = mt * CV_BM, n0 = nt * BN;
     const int t = threadIdx.x, lane = t & 63;
@@ -296,20 +264,7 @@ conv_igemm_dma_kernel(ConvP p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int chunk = lc ^ ((lane >> 4) | ((i & 1) << 2));
-        const int m = m0 + wave * 32 + 8 * i + lr;
-        aoff[i] = 0; amask[i] = 0;
-        if (m < p.M) {
-            if (p.simple) { aoff[i] = (m * p.Cin + chunk * 8) * 2; amask[i] = 1u; continue; }
-            int q1 = (int)((float)m * p.inv_wo), wo = m - q1 * p.Wo;
-            if (wo < 0) { --q1; wo += p.Wo; } else if (wo >= p.Wo) { ++q1; wo -= p.Wo; }
-            int n = (int)((float)q1 * p.inv_ho), ho = q1 - n * p.Ho;
-            if (ho < 0) { --n; ho += p.Ho; } else if (ho >= p.Ho) { ++n; ho -= p.Ho; }
-            const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
-            aoff[i] = (((n * p.H + hi0) * p.W + wi0) * p.Cin + chunk * 8) * 2;
-            for (int r = 0; r < p.R; ++r)
-                for (int s2 = 0; s2 < p.S; ++s2)
-                    if ((unsigned)(hi0 + r) < (unsigned)p.H && (unsigned)(wi0 + s2) < (unsigned)p.W) amask[i] |= 1u << (r * p.S + s2);
-        }
+        cv_row_origin(p, m0 + wave * 32 + 8 * i + lr, chunk, aoff[i], amask[i]);
     }
     const int K = p.KT * CV_BK;
     int woff[BI];
@@ -318,10 +273,7 @@ conv_igemm_dma_kernel(ConvP p) {
         const int chunk = lc ^ ((lane >> 4) | ((i & 1) << 2));
         woff[i] = ((n0 + wave * 8 * BI + 8 * i + lr) * K + chunk * 8) * 2;
     }
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), (short)0,
-                                                                           (int)((unsigned)(p.N * p.H * p.W) * (unsigned)p.Cin * 2u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w), (short)0,
-                                                                           (int)((unsigned)p.Cout * (unsigned)K * 2u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = cv_rsrc_x(p), rs_w = cv_rsrc_w(p, K);
     uint32_t af[MI][4], bf[NI][4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
@@ -376,12 +328,7 @@ conv_igemm_dma_kernel(ConvP p) {
     }
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.0f;
+    cv_zero_acc(acc);
 
     if (NST == 1) {
         for (int kt = 0; kt < p.KT; ++kt) {
@@ -442,11 +389,7 @@ conv_igemm_big_kernel(ConvP p, int ntn2, int nblocks2) {
     using G = CvbGeom<TM, TN, NST>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int MI = 2, NI = 2;
-    int lin;
-    {
-        const int b = blockIdx.x, q = nblocks2 / 8, r = nblocks2 % 8, xcd = b % 8, i = b / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    const int lin = cv_xcd_tile(blockIdx.x, nblocks2);
     const int mt2 = lin / ntn2, nt2 = lin - mt2 * ntn2;
     const int m0 = mt2 * TM, n0 = nt2 * TN;
     const int t = threadIdx.x, lane = t & 63;
@@ -459,20 +402,7 @@ conv_igemm_big_kernel(ConvP p, int ntn2, int nblocks2) {
 #pragma unroll
     for (int i = 0; i < G::APW; ++i) {
         const int chunk = lc ^ ((lane >> 4) | ((i & 1) << 2));
-        const int m = m0 + wave * (TM / G::NW) + 8 * i + lr;
-        aoff[i] = 0; amask[i] = 0;
-        if (m < p.M) {
-            if (p.simple) { aoff[i] = (m * p.Cin + chunk * 8) * 2; amask[i] = 1u; continue; }
-            int q1 = (int)((float)m * p.inv_wo), wo = m - q1 * p.Wo;
-            if (wo < 0) { --q1; wo += p.Wo; } else if (wo >= p.Wo) { ++q1; wo -= p.Wo; }
-            int n = (int)((float)q1 * p.inv_ho), ho = q1 - n * p.Ho;
-            if (ho < 0) { --n; ho += p.Ho; } else if (ho >= p.Ho) { ++n; ho -= p.Ho; }
-            const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
-            aoff[i] = (((n * p.H + hi0) * p.W + wi0) * p.Cin + chunk * 8) * 2;
-            for (int r = 0; r < p.R; ++r)
-                for (int s2 = 0; s2 < p.S; ++s2)
-                    if ((unsigned)(hi0 + r) < (unsigned)p.H && (unsigned)(wi0 + s2) < (unsigned)p.W) amask[i] |= 1u << (r * p.S + s2);
-        }
+        cv_row_origin(p, m0 + wave * (TM / G::NW) + 8 * i + lr, chunk, aoff[i], amask[i]);
     }
     const int K = p.KT * CV_BK;
     int woff[G::BPW];
@@ -481,10 +411,7 @@ conv_igemm_big_kernel(ConvP p, int ntn2, int nblocks2) {
         const int chunk = lc ^ ((lane >> 4) | ((i & 1) << 2));
         woff[i] = ((n0 + wave * (TN / G::NW) + 8 * i + lr) * K + chunk * 8) * 2;
     }
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), (short)0,
-                                                                           (int)((unsigned)(p.N * p.H * p.W) * (unsigned)p.Cin * 2u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w), (short)0,
-                                                                           (int)((unsigned)p.Cout * (unsigned)K * 2u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = cv_rsrc_x(p), rs_w = cv_rsrc_w(p, K);
     uint32_t af[MI][4], bf[NI][4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
@@ -533,12 +460,7 @@ conv_igemm_big_kernel(ConvP p, int ntn2, int nblocks2) {
         }                                                                                                       \
     }
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.0f;
+    cv_zero_acc(acc);
     if (NST == 1) {
         for (int kt = 0; kt < p.KT; ++kt) {
             CVB_ISSUE(0);
@@ -607,11 +529,7 @@ conv3x3_patch_kernel(ConvP p) {
     // LDS: [patch stage 0][patch stage 1 (only used when Cin > 64)][B stage 0][B stage 1]
     const int npatch = (NST == 2 && p.cpk > 1) ? 2 : 1;
     const uint32_t b_base = (uint32_t)(npatch * G::PATCH);
-    int lin;
-    {
-        const int b = blockIdx.x, q = p.nblocks / 8, r = p.nblocks % 8, xcd = b % 8, i = b / 8;
-        lin = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    const int lin = cv_xcd_tile(blockIdx.x, p.nblocks);
     const int mt = lin / p.ntn, nt = lin - mt * p.ntn;    // mt = chunk index
     const int n_img = mt / G::CPI, h0 = (mt - n_img * G::CPI) * G::RB;
     const int m0 = (n_img * WI + h0) * WI, n0 = nt * BN;
@@ -675,12 +593,7 @@ conv3x3_patch_kernel(ConvP p) {
         }
 
     f32x16 acc[MI][NI];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.0f;
+    cv_zero_acc(acc);
 
 #define CP_ISSUE_PATCH(cb, ps)                                                                                  \
     {                                                                                                           \
@@ -869,6 +782,17 @@ extern "C" int dir_conv_dgrad_s2(const void* dy, const void* wcls, void* dx, int
     return conv_dgrad_s2_impl(dy, wcls, dx, N, Ho, Wo, Cy, Cx, nullptr, nullptr, 0, DIR_CONV_AUTO, stream);
 }
 
+// The fused BatchNorm-backward arguments of the dir_conv_dgrad_*bnstats / *_ex entry points, validated in one place: bn_x and stats come
+// together, bn_x is 16-byte aligned, and bn_gamma (the BatchNorm is followed by a ReLU) brings bn_x and the other three vectors along.
+// (The *_bnstats entry points, where the fusion is not optional, refuse a null bn_x themselves.)
+static int conv_bn_from_args(const void* bn_x, const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_rstd,
+                             const void* mask_bits, const float* stats, ConvBn* bn) {
+    DIR_RETURN_IF((bn_x == nullptr) != (stats == nullptr) || (bn_x && !dir_aligned16(bn_x)), DIR_EINVAL);
+    DIR_RETURN_IF(bn_gamma && (!bn_x || !bn_beta || !bn_mean || !bn_rstd), DIR_EINVAL);
+    *bn = ConvBn{bn_x, bn_gamma, bn_beta, bn_mean, bn_rstd, mask_bits};
+    return DIR_OK;
+}
+
 // The data gradients above with the FIRST pass of the BatchNorm backward that consumes them fused into the store loop
 // (dir_bn_bwd_partials is the rest): bn_x = the input of that BatchNorm ([N, H', W', Cout] like the result), stats =
 // [stats_rows][2][Cout] floats, stats_rows = dir_conv_plan_rows(...) (4 x dir_conv_stats_rows(N, Ho, Wo) for the stride-2 form: one
@@ -878,8 +802,10 @@ extern "C" int dir_conv_dgrad_bnstats(const void* x, const void* w, const void* 
                                       const void* relu_mask, void* y, int N, int H, int W, int Cin, int Cout, int R, int S,
                                       int pad, const void* bn_x, const float* bn_gamma, const float* bn_beta,
                                       const float* bn_mean, const float* bn_rstd, float* stats, int stats_rows, dir_stream_t stream) {
-    DIR_RETURN_IF(!bn_x || !stats || !dir_aligned16(bn_x) || (bn_gamma && (!bn_beta || !bn_mean || !bn_rstd)), DIR_EINVAL);
-    const ConvBn bn{bn_x, bn_gamma, bn_beta, bn_mean, bn_rstd, nullptr};
+    ConvBn bn;
+    DIR_RETURN_IF(!bn_x, DIR_EINVAL);
+    const int rc = conv_bn_from_args(bn_x, bn_gamma, bn_beta, bn_mean, bn_rstd, nullptr, stats, &bn);
+    if (rc != DIR_OK) return rc;
     return conv_launch_ex(x, w, addend, addend_s2, relu_mask, y, stats, stats_rows, N, H, W, Cin, Cout, R, S, 1, pad, -1, 0, DIR_CONV_AUTO, stream, &bn);
 }
 
@@ -891,17 +817,19 @@ extern "C" int dir_conv_dgrad_ex(const void* x, const void* w, const void* adden
                                  const void* relu_mask_bits, void* y, int N, int H, int W, int Cin, int Cout, int R, int S, int pad,
                                  const void* bn_x, const float* bn_gamma, const float* bn_beta, const float* bn_mean,
                                  const float* bn_rstd, float* stats, int stats_rows, int variant, dir_stream_t stream) {
-    DIR_RETURN_IF((bn_x == nullptr) != (stats == nullptr) || (bn_x && !dir_aligned16(bn_x)), DIR_EINVAL);
-    DIR_RETURN_IF(bn_gamma && (!bn_x || !bn_beta || !bn_mean || !bn_rstd), DIR_EINVAL);
-    const ConvBn bn{bn_x, bn_gamma, bn_beta, bn_mean, bn_rstd, relu_mask_bits};
+    ConvBn bn;
+    const int rc = conv_bn_from_args(bn_x, bn_gamma, bn_beta, bn_mean, bn_rstd, relu_mask_bits, stats, &bn);
+    if (rc != DIR_OK) return rc;
     return conv_launch_ex(x, w, addend, addend_s2, relu_mask, y, stats, stats_rows, N, H, W, Cin, Cout, R, S, 1, pad, -1, 0, variant, stream, &bn);
 }
 
 extern "C" int dir_conv_dgrad_s2_bnstats(const void* dy, const void* wcls, void* dx, int N, int Ho, int Wo, int Cy, int Cx,
                                          const void* bn_x, const float* bn_gamma, const float* bn_beta, const float* bn_mean,
                                          const float* bn_rstd, float* stats, int stats_rows, dir_stream_t stream) {
-    DIR_RETURN_IF(!bn_x || !stats || !dir_aligned16(bn_x) || (bn_gamma && (!bn_beta || !bn_mean || !bn_rstd)), DIR_EINVAL);
-    const ConvBn bn{bn_x, bn_gamma, bn_beta, bn_mean, bn_rstd, nullptr};
+    ConvBn bn;
+    DIR_RETURN_IF(!bn_x, DIR_EINVAL);
+    const int rc = conv_bn_from_args(bn_x, bn_gamma, bn_beta, bn_mean, bn_rstd, nullptr, stats, &bn);
+    if (rc != DIR_OK) return rc;
     return conv_dgrad_s2_impl(dy, wcls, dx, N, Ho, Wo, Cy, Cx, &bn, stats, stats_rows, DIR_CONV_AUTO, stream);
 }
 
@@ -909,10 +837,36 @@ extern "C" int dir_conv_dgrad_s2_bnstats(const void* dy, const void* wcls, void*
 extern "C" int dir_conv_dgrad_s2_ex(const void* dy, const void* wcls, void* dx, int N, int Ho, int Wo, int Cy, int Cx,
                                     const void* bn_x, const float* bn_gamma, const float* bn_beta, const float* bn_mean,
                                     const float* bn_rstd, float* stats, int stats_rows, int variant, dir_stream_t stream) {
-    DIR_RETURN_IF((bn_x == nullptr) != (stats == nullptr) || (bn_x && !dir_aligned16(bn_x)), DIR_EINVAL);
-    DIR_RETURN_IF(bn_gamma && (!bn_x || !bn_beta || !bn_mean || !bn_rstd), DIR_EINVAL);
-    const ConvBn bn{bn_x, bn_gamma, bn_beta, bn_mean, bn_rstd, nullptr};
+    ConvBn bn;
+    const int rc = conv_bn_from_args(bn_x, bn_gamma, bn_beta, bn_mean, bn_rstd, nullptr, stats, &bn);
+    if (rc != DIR_OK) return rc;
     return conv_dgrad_s2_impl(dy, wcls, dx, N, Ho, Wo, Cy, Cx, bn_x ? &bn : nullptr, stats, stats_rows, variant, stream);
+}
+
+// The kernels' parameter block from the (validated) launch arguments; 128-row M tiles (the patch-staged launch overrides nblocks).
+static ConvP conv_params(const void* x, const void* w, const void* addend, const void* addend_s2, const void* relu_mask, void* y, float* stats,
+                         const ConvBn* bn, int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int Ho, int Wo,
+                         int cls_a, int cls_b, bool wide) {
+    const bool cls = cls_a >= 0;
+    ConvP p{};
+    p.x = static_cast<const uint16_t*>(x); p.w = static_cast<const uint16_t*>(w); p.y = static_cast<uint16_t*>(y);
+    p.stats = stats;
+    p.addend = static_cast<const uint16_t*>(addend);
+    p.mask = static_cast<const uint16_t*>(relu_mask);
+    p.addend2 = static_cast<const uint16_t*>(addend_s2);
+    if (bn) {
+        p.mask_bits = static_cast<const uint8_t*>(bn->mask_bits);
+        p.bnx = static_cast<const uint16_t*>(bn->x);
+        p.bn_gamma = bn->gamma; p.bn_beta = bn->beta; p.bn_mean = bn->mean; p.bn_rstd = bn->rstd;
+    }
+    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.R = R; p.S = S; p.stride = stride; p.pad = pad;
+    p.M = N * Ho * Wo; p.cpk = Cin / CV_BK; p.KT = R * S * p.cpk;
+    p.simple = (R == 1 && S == 1 && stride == 1 && pad == 0) ? 1 : 0;
+    p.inv_wo = 1.0f / (float)Wo; p.inv_ho = 1.0f / (float)Ho;
+    p.o2 = cls ? 1 : 0; p.o_a = cls ? cls_a : 0; p.o_b = cls ? cls_b : 0; p.OH = 2 * H; p.OW = 2 * W;
+    p.ntn = wide ? Cout / 128 : Cout / 64;
+    p.nblocks = (p.M + CV_BM - 1) / CV_BM * p.ntn;
+    return p;
 }
 
 // cls_a >= 0: parity class (cls_a, cls_b) of a stride-2 data gradient: x = dY [N, H, W, Cin], kernel (1 + a) x (1 + b)
@@ -942,26 +896,11 @@ static int conv_launch_ex(const void* x, const void* w, const void* addend, cons
     const ConvPlan plan = conv_plan(N, H, W, Cin, Cout, R, S, stride, pad, Ho, Wo, addend && addend_s2, cls, variant);
     DIR_RETURN_IF(plan.kind == CK_UNSUPPORTED, (variant < 0 || variant > DIR_CONV_BIG || variant == 4) ? DIR_EINVAL : DIR_EUNSUPPORTED);
     DIR_RETURN_IF(stats && (size_t)stats_rows != plan.rows, DIR_EINVAL);
-    ConvP p;
-    p.x = static_cast<const uint16_t*>(x); p.w = static_cast<const uint16_t*>(w); p.y = static_cast<uint16_t*>(y);
-    p.stats = stats;
-    p.addend = static_cast<const uint16_t*>(addend);
-    p.mask = static_cast<const uint16_t*>(relu_mask);
-    p.addend2 = static_cast<const uint16_t*>(addend_s2);
-    p.mask_bits = bn ? static_cast<const uint8_t*>(bn->mask_bits) : nullptr;
-    p.bnx = bn ? static_cast<const uint16_t*>(bn->x) : nullptr;
-    p.bn_gamma = bn ? bn->gamma : nullptr; p.bn_beta = bn ? bn->beta : nullptr;
-    p.bn_mean = bn ? bn->mean : nullptr; p.bn_rstd = bn ? bn->rstd : nullptr;
-    p.N = N; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cout; p.R = R; p.S = S; p.stride = stride; p.pad = pad;
-    p.M = (int)M; p.cpk = Cin / CV_BK; p.KT = R * S * p.cpk;
-    p.simple = (R == 1 && S == 1 && stride == 1 && pad == 0) ? 1 : 0;
-    p.inv_wo = 1.0f / (float)Wo; p.inv_ho = 1.0f / (float)Ho;
-    p.o2 = cls ? 1 : 0; p.o_a = cls ? cls_a : 0; p.o_b = cls ? cls_b : 0; p.OH = 2 * H; p.OW = 2 * W;
-    DIR_RETURN_IF(cls && (long long)N * 4 * H * W * Cout >= (1ll << 31), DIR_EUNSUPPORTED);
-    const int mtiles = (int)((M + CV_BM - 1) / CV_BM);
     const bool wide = (Cout % 128 == 0);
-    p.ntn = wide ? Cout / 128 : Cout / 64;
-    p.nblocks = mtiles * p.ntn;
+    ConvP p = conv_params(x, w, addend, addend_s2, relu_mask, y, stats, bn, N, H, W, Cin, Cout, R, S, stride, pad, Ho, Wo, cls_a, cls_b, wide);
+    DIR_RETURN_IF(cls && (long long)N * 4 * H * W * Cout >= (1ll << 31), DIR_EUNSUPPORTED);
+    // lean = no fused operand (the plain forward): those kernel forms drop the fused code paths and fit four workgroups per CU
+    const bool lean = !p.addend && !p.addend2 && !p.mask && !p.mask_bits && !p.bnx && !p.o2;
     hipStream_t s = dir_s(stream);
     const int tile_n = wide ? 128 : 64;
     const int stage = CV_BM * (tile_n * 2 + 16) + 4 * 2 * tile_n * 4;      // epilogue staging + column partials
@@ -983,11 +922,10 @@ static int conv_launch_ex(const void* x, const void* w, const void* addend, cons
     if (plan.kind == CK_BIG) {
         // 256 x 256 CU tile on 16 wavefronts (half the LDS-DMA pieces per FLOP)
         using G = CvbGeom<256, 256, 2>;
-        const bool leanb = !p.addend && !p.addend2 && !p.mask && !p.mask_bits && !p.bnx && !p.o2;
         DIR_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_big_kernel<256, 256, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
                             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_big_kernel<256, 256, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
         const int ntn2 = Cout / 256, nb2 = (int)(M / 256) * ntn2;
-        if (leanb) hipLaunchKernelGGL((conv_igemm_big_kernel<256, 256, 2, true>), dim3(nb2), dim3(G::THREADS), G::LDS, s, p, ntn2, nb2);
+        if (lean) hipLaunchKernelGGL((conv_igemm_big_kernel<256, 256, 2, true>), dim3(nb2), dim3(G::THREADS), G::LDS, s, p, ntn2, nb2);
         else hipLaunchKernelGGL((conv_igemm_big_kernel<256, 256, 2, false>), dim3(nb2), dim3(G::THREADS), G::LDS, s, p, ntn2, nb2);
         DIR_LAUNCH_CHECK();
         return DIR_OK;
@@ -1015,8 +953,6 @@ static int conv_launch_ex(const void* x, const void* w, const void* addend, cons
     DIR_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<128, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
                         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_igemm_kernel<128, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
 #define CV_LAUNCH(BN_, PF_, NB_) hipLaunchKernelGGL((conv_igemm_kernel<BN_, PF_, NB_>), dim3(p.nblocks), dim3(DIR_TPB), lds2, s, p)
-    // lean = no fused operand (the plain forward): the single-stage kernel then fits four workgroups per CU
-    const bool lean = !p.addend && !p.addend2 && !p.mask && !p.mask_bits && !p.bnx && !p.o2;
     // 128-wide tiles, short K loops (<= 18 steps): the single-stage LDS-DMA kernel, FOUR workgroups per CU (114 registers, 39 KB
     // of LDS) instead of three — throughput of these launches follows the resident workgroups (profiles/r02_conv_occupancy_sensitivity.txt;
     // A/B per train step -0.8 ms, per epoch-tail forward -0.7 ms). The 64-wide register-staged kernel already runs four per CU
@@ -1028,215 +964,6 @@ static int conv_launch_ex(const void* x, const void* w, const void* addend, cons
     else if (wide) { if (pf == 2) CV_LAUNCH(128, 2, 2); else if (p.nbuf == 2) CV_LAUNCH(128, 1, 2); else CV_LAUNCH(128, 1, 1); }
     else           { if (pf == 2) CV_LAUNCH(64, 2, 2);  else if (p.nbuf == 2) CV_LAUNCH(64, 1, 2);  else CV_LAUNCH(64, 1, 1); }
 #undef CV_LAUNCH
-    DIR_LAUNCH_CHECK();
-    return DIR_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Weight preparation: one launch per conv layer and optimizer step turns the float32 master weight
-// [Cout][R][S][Cin] into the two bf16 operands the MFMA kernels consume — w16 (same layout, forward / wgrad shape)
-// and, optionally, w16_rot [Cin][R][S][Cout] with the taps rotated by 180 degrees (the data-gradient convolution's
-// weight) — instead of a cast + flip + permute + copy chain of library kernels.
-namespace {
-// One layer: w [Cout][RS][Cin] f32 -> w16 (same layout, bf16) and optionally w16_rot [Cin][RS][Cout] with the taps
-// reversed. Cin, Cout % 64 == 0: the (co, ci) transpose of each tap goes through a 64x64 LDS tile, so both the float
-// reads (256 B rows) and the two bf16 writes (128 B rows) are coalesced. Tiles are strided over gridDim.x.
-// rot_mode 0: w16_rot = [Cin][R][S][Cout] with the taps rotated by 180 degrees (stride-1 data gradient).
-// rot_mode 1 (3x3 only): w16_rot = the four parity-class weights of the STRIDE-2 data gradient, packed back to back:
-//   class (a, b) = (r != 1, s != 1) holds the (1 + a) x (1 + b) taps that reach output pixels (2 i + a, 2 j + b), as
-//   [Cin][(1 + a)(1 + b)][Cout] with tap (dr, ds) = (r == 0, s == 0) (dY row i + dr, column j + ds); class bases at
-//   0, 1, 3, 5 taps.
-__device__ __forceinline__ size_t conv_prep_rot_index(int rot_mode, int ci, int tap, int co, int RS, int Cin, int Cout) {
-    if (rot_mode == 0) return ((size_t)ci * RS + (RS - 1 - tap)) * Cout + co;
-    const int r = tap / 3, s = tap - 3 * r;
-    const int a = r != 1, b = s != 1, dr = r == 0, ds = s == 0;
-    const int taps = (1 + a) * (1 + b), t = dr * (1 + b) + ds;
-    const int base = a ? (b ? 5 : 3) : (b ? 1 : 0);
-    return (size_t)base * Cin * Cout + ((size_t)ci * taps + t) * Cout + co;
-}
-
-// Adam (torch.optim.Adam's single-tensor arithmetic, no amsgrad): one element; returns the new parameter value
-struct AdamH { float step_size, beta2, one_minus_beta1, one_minus_beta2, eps, weight_decay, bias_correction2_sqrt; };   // (host: float64, then rounded, like torch's Python scalars)
-__device__ __forceinline__ float adam_update(float p, float g, float* __restrict__ m, float* __restrict__ v, size_t i, const AdamH& h) {
-    if (h.weight_decay != 0.0f) g = g + h.weight_decay * p;                      // grad.add(param, alpha=weight_decay)
-    const float m0 = m[i], v0 = v[i];
-    const float m1 = m0 + h.one_minus_beta1 * (g - m0);                           // exp_avg.lerp_(grad, 1 - beta1)
-    const float v1 = v0 * h.beta2 + h.one_minus_beta2 * (g * g);                  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-    m[i] = m1; v[i] = v1;
-    const float denom = sqrtf(v1) / h.bias_correction2_sqrt + h.eps;              // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-    return p - h.step_size * (m1 / denom);                                        // param.addcdiv_(exp_avg, denom, value=-step_size), step_size = lr / bias_correction1
-}
-
-// torch.optim.SGD's single-tensor arithmetic (sgd.py: _single_tensor_sgd), one element; returns the new parameter value. The `add(x, alpha=a)`
-// steps are written as fmaf, which is how torch's element-wise kernels evaluate `a + alpha * b`.
-struct SgdH { float lr, momentum, one_minus_dampening, weight_decay; int nesterov, first; };
-__device__ __forceinline__ float sgd_update(float p, float g, float* __restrict__ buf, size_t i, const SgdH& h) {
-    if (h.weight_decay != 0.0f) g = __fmaf_rn(h.weight_decay, p, g);                 // grad = grad.add(param, alpha=weight_decay)
-    if (h.momentum != 0.0f) {
-        const float b = h.first ? g : __fmaf_rn(h.one_minus_dampening, g, buf[i] * h.momentum);   // buf = clone(grad) | buf.mul_(momentum).add_(grad, alpha=1 - dampening)
-        buf[i] = b;
-        g = h.nesterov ? __fmaf_rn(h.momentum, b, g) : b;                             // grad = grad.add(buf, alpha=momentum) | buf
-    }
-    return __fmaf_rn(-h.lr, g, p);                                                    // param.add_(grad, alpha=-lr)
-}
-// what the weight preparation pass does to the master weight first: nothing, an Adam step, an SGD step
-struct OptNone { __device__ __forceinline__ float operator()(float w, size_t) const { return w; } static constexpr bool UPDATES = false; };
-struct OptAdam { const float* g; float* m; float* v; AdamH h; static constexpr bool UPDATES = true;
-                 __device__ __forceinline__ float operator()(float w, size_t i) const { return adam_update(w, g[i], m, v, i, h); } };
-struct OptSgd { const float* g; float* buf; SgdH h; static constexpr bool UPDATES = true;
-                __device__ __forceinline__ float operator()(float w, size_t i) const { return sgd_update(w, g[i], buf, i, h); } };
-
-// OPT::UPDATES: w is first UPDATED in place from (g, m, v) — the optimizer step — and the bf16 operands are made from the new value in the
-// same pass (dir_adam_step): one read of the master weight for the optimizer and the two layout conversions together.
-template <typename OPT = OptNone>
-__device__ __forceinline__ void conv_prep_body(float* __restrict__ w, int Cout, int RS, int Cin,
-                                               uint16_t* __restrict__ w16, uint16_t* __restrict__ w16_rot, int rot_mode,
-                                               const OPT opt = OPT{}) {
-    __shared__ uint16_t tile[64][66];
-    const int t = threadIdx.x, tx = t & 63, ty = t >> 6;           // 4 rows of 64 per pass
-    if ((Cout & 63) || (Cin & 63)) {                               // generic fallback (not used by ResNet-50's layers)
-        const size_t n = (size_t)Cout * RS * Cin;
-        for (size_t i = (size_t)blockIdx.x * DIR_TPB + t; i < n; i += (size_t)gridDim.x * DIR_TPB) {
-            float wv = w[i];
-            if (OPT::UPDATES) { wv = opt(wv, i); w[i] = wv; }
-            const uint16_t h = (uint16_t)cv_f2bf(wv);
-            w16[i] = h;
-            if (w16_rot) {
-                const int ci = (int)(i % Cin); const size_t t1 = i / Cin; const int tap = (int)(t1 % RS); const int co = (int)(t1 / RS);
-                w16_rot[conv_prep_rot_index(rot_mode, ci, tap, co, RS, Cin, Cout)] = h;
-            }
-        }
-        return;
-    }
-    const int tci = Cin >> 6, tco = Cout >> 6, ntiles = tci * tco * RS;
-    for (int tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
-        const int ci0 = (tl % tci) << 6; const int t1 = tl / tci; const int tap = t1 % RS; const int co0 = (t1 / RS) << 6;
-#pragma unroll 4
-        for (int r = ty; r < 64; r += 4) {                         // row = output channel, 64 consecutive input channels
-            const size_t i = ((size_t)(co0 + r) * RS + tap) * Cin + ci0 + tx;
-            float wv = w[i];
-            if (OPT::UPDATES) { wv = opt(wv, i); w[i] = wv; }
-            const uint16_t hb = (uint16_t)cv_f2bf(wv);
-            w16[i] = hb;
-            tile[r][tx] = hb;
-        }
-        if (w16_rot) {
-            __syncthreads();
-#pragma unroll 4
-            for (int r = ty; r < 64; r += 4)                       // row = input channel, 64 consecutive output channels
-                w16_rot[conv_prep_rot_index(rot_mode, ci0 + r, tap, co0 + tx, RS, Cin, Cout)] = tile[tx][r];
-            __syncthreads();
-        }
-    }
-}
-
-__global__ void __launch_bounds__(DIR_TPB)
-conv_prep_weights_kernel(const float* __restrict__ w, int Cout, int RS, int Cin, uint16_t* __restrict__ w16,
-                         uint16_t* __restrict__ w16_rot, int rot_mode) {
-    conv_prep_body(const_cast<float*>(w), Cout, RS, Cin, w16, w16_rot, rot_mode);
-}
-
-// blockIdx.y = layer; the layer's row of the table holds its pointers and extents
-__global__ void __launch_bounds__(DIR_TPB)
-conv_prep_weights_batched_kernel(const long long* __restrict__ table) {
-    const long long* e = table + (size_t)blockIdx.y * 7;
-    conv_prep_body(reinterpret_cast<float*>(e[0]), (int)e[3], (int)e[4], (int)e[5],
-                   reinterpret_cast<uint16_t*>(e[1]), reinterpret_cast<uint16_t*>(e[2]), (int)e[6]);
-}
-}  // namespace
-
-namespace {
-// One Adam step for EVERY parameter tensor of the network in one launch (blockIdx.y = tensor; row of the table = 12 int64:
-// param, grad, exp_avg, exp_avg_sq, numel, w16, w16_rot, Cout, RS, Cin, rot_mode, 0). Rows with w16 != 0 are convolution weights:
-// their bf16 operands for the next forward / data gradient are rewritten from the updated value in the same pass.
-__global__ void __launch_bounds__(DIR_TPB)
-adam_step_kernel(const long long* __restrict__ table, AdamH h) {
-    const long long* e = table + (size_t)blockIdx.y * 12;
-    float* w = reinterpret_cast<float*>(e[0]);
-    const float* g = reinterpret_cast<const float*>(e[1]);
-    float* m = reinterpret_cast<float*>(e[2]);
-    float* v = reinterpret_cast<float*>(e[3]);
-    if (e[5]) {
-        conv_prep_body<OptAdam>(w, (int)e[7], (int)e[8], (int)e[9], reinterpret_cast<uint16_t*>(e[5]), reinterpret_cast<uint16_t*>(e[6]), (int)e[10], OptAdam{g, m, v, h});
-        return;
-    }
-    const size_t n = (size_t)e[4];
-    for (size_t i = (size_t)blockIdx.x * DIR_TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * DIR_TPB)
-        w[i] = adam_update(w[i], g[i], m, v, i, h);
-}
-
-// The same launch shape for torch.optim.SGD (rows: param, grad, momentum_buffer (0 = no momentum), 0, numel, w16, w16_rot, Cout, RS, Cin, rot_mode, 0)
-__global__ void __launch_bounds__(DIR_TPB)
-sgd_step_kernel(const long long* __restrict__ table, SgdH h) {
-    const long long* e = table + (size_t)blockIdx.y * 12;
-    float* w = reinterpret_cast<float*>(e[0]);
-    const float* g = reinterpret_cast<const float*>(e[1]);
-    float* buf = reinterpret_cast<float*>(e[2]);
-    if (e[5]) {
-        conv_prep_body<OptSgd>(w, (int)e[7], (int)e[8], (int)e[9], reinterpret_cast<uint16_t*>(e[5]), reinterpret_cast<uint16_t*>(e[6]), (int)e[10], OptSgd{g, buf, h});
-        return;
-    }
-    const size_t n = (size_t)e[4];
-    for (size_t i = (size_t)blockIdx.x * DIR_TPB + threadIdx.x; i < n; i += (size_t)gridDim.x * DIR_TPB)
-        w[i] = sgd_update(w[i], g[i], buf, i, h);
-}
-}  // namespace
-
-// torch.optim.SGD.step() (train.py:163-164 builds it for --optimizer sgd) for all parameters in ONE launch, fused with the bf16 weight
-// preparation like dir_adam_step. table: device [ntensors][12] int64 (see sgd_step_kernel). first != 0: the momentum buffers do not
-// hold a value yet (torch creates them as clone(grad) at the first step); momentum == 0: no buffer is touched (entries may be 0).
-extern "C" int dir_sgd_step(const void* table, int ntensors, double lr, double momentum, double dampening, double weight_decay, int nesterov,
-                            int first, dir_stream_t stream) {
-    DIR_RETURN_IF(!table || ntensors <= 0 || ntensors > 65535, DIR_EINVAL);
-    DIR_RETURN_IF(nesterov && (momentum <= 0.0 || dampening != 0.0), DIR_EINVAL);       // torch: "Nesterov momentum requires a momentum and zero dampening"
-    SgdH h;
-    h.lr = (float)lr; h.momentum = (float)momentum; h.one_minus_dampening = (float)(1.0 - dampening); h.weight_decay = (float)weight_decay;
-    h.nesterov = nesterov ? 1 : 0; h.first = first ? 1 : 0;
-    hipLaunchKernelGGL(sgd_step_kernel, dim3(128, ntensors), dim3(DIR_TPB), 0, dir_s(stream), static_cast<const long long*>(table), h);
-    DIR_LAUNCH_CHECK();
-    return DIR_OK;
-}
-
-// torch.optim.Adam.step() (train.py:161-162 builds the optimizer, :259-260 steps it) for all parameters in ONE launch, fused with
-// the bf16 weight preparation of the convolution layers (dir_conv_prep_weights_batched). table: device [ntensors][12] int64 (see
-// adam_step_kernel); step >= 1 is the step count AFTER the increment (bias corrections 1 - beta^step, computed on the host in
-// float64 like torch's non-capturable path). float32 parameters, gradients and state, all dense.
-extern "C" int dir_adam_step(const void* table, int ntensors, double lr, double beta1, double beta2, double eps, double weight_decay,
-                             long long step, dir_stream_t stream) {
-    DIR_RETURN_IF(!table || ntensors <= 0 || ntensors > 65535 || step < 1, DIR_EINVAL);
-    AdamH h;
-    h.beta2 = (float)beta2; h.one_minus_beta1 = (float)(1.0 - beta1); h.one_minus_beta2 = (float)(1.0 - beta2);
-    h.eps = (float)eps; h.weight_decay = (float)weight_decay;
-    h.step_size = (float)(lr / (1.0 - pow(beta1, (double)step)));
-    h.bias_correction2_sqrt = (float)sqrt(1.0 - pow(beta2, (double)step));
-    hipLaunchKernelGGL(adam_step_kernel, dim3(128, ntensors), dim3(DIR_TPB), 0, dir_s(stream), static_cast<const long long*>(table), h);
-    DIR_LAUNCH_CHECK();
-    return DIR_OK;
-}
-
-extern "C" int dir_conv_prep_weights_batched(const void* table, int nlayers, dir_stream_t stream) {
-    DIR_RETURN_IF(!table || nlayers <= 0 || nlayers > 65535, DIR_EINVAL);
-    hipLaunchKernelGGL(conv_prep_weights_batched_kernel, dim3(128, nlayers), dim3(DIR_TPB), 0, dir_s(stream),
-                       static_cast<const long long*>(table));
-    DIR_LAUNCH_CHECK();
-    return DIR_OK;
-}
-
-extern "C" int dir_conv_prep_weights_ex(const float* w, int Cout, int R, int S, int Cin, void* w16, void* w16_rot,
-                                        int rot_mode, dir_stream_t stream);
-extern "C" int dir_conv_prep_weights(const float* w, int Cout, int R, int S, int Cin, void* w16, void* w16_rot,
-                                     dir_stream_t stream) {
-    return dir_conv_prep_weights_ex(w, Cout, R, S, Cin, w16, w16_rot, 0, stream);
-}
-
-extern "C" int dir_conv_prep_weights_ex(const float* w, int Cout, int R, int S, int Cin, void* w16, void* w16_rot,
-                                        int rot_mode, dir_stream_t stream) {
-    DIR_RETURN_IF(!w || !w16 || Cout <= 0 || R <= 0 || S <= 0 || Cin <= 0, DIR_EINVAL);
-    DIR_RETURN_IF(rot_mode < 0 || rot_mode > 1 || (rot_mode == 1 && (R != 3 || S != 3)), DIR_EINVAL);
-    const size_t n = (size_t)Cout * R * S * Cin;
-    int grid = dir_cdiv((long long)n, DIR_TPB); if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(conv_prep_weights_kernel, dim3(grid), dim3(DIR_TPB), 0, dir_s(stream), w, Cout, R * S, Cin,
-                       static_cast<uint16_t*>(w16), static_cast<uint16_t*>(w16_rot), rot_mode);
     DIR_LAUNCH_CHECK();
     return DIR_OK;
 }

@@ -36,6 +36,60 @@ __device__ __forceinline__ void cv_epilogue_stats(const ConvP& p, float (&ssum)[
     }
 }
 
+// ---- arithmetic of ONE row chunk: cw = 8 consecutive channels of a staged row as four packed bf16 pairs (low half = even channel).
+// Both store loops of cv_epilogue_staged (and, for the statistics, its LEAN branch) call these and nothing else between their loads
+// and stores, so the order of floating-point operations per element and per partial sum has one definition.
+__device__ __forceinline__ float cv_bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float cv_bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+__device__ __forceinline__ cv_u32x4 cv_vec(const uint4& v) { return cv_u32x4{v.x, v.y, v.z, v.w}; }
+
+// BatchNorm statistics of the ROUNDED outputs (what the following BatchNorm reads): (sum, sum of squares) of this thread's 8 channels
+__device__ __forceinline__ void cv_row_fwd_stats(const uint32_t (&cw)[4], float (&ssum)[8], float (&ssq)[8]) {
+#pragma unroll
+    for (int q2 = 0; q2 < 4; ++q2) {
+        const float f0 = cv_bf_lo(cw[q2]), f1 = cv_bf_hi(cw[q2]);
+        ssum[2 * q2] += f0; ssq[2 * q2] += f0 * f0; ssum[2 * q2 + 1] += f1; ssq[2 * q2 + 1] += f1 * f1;
+    }
+}
+// y = bf16(bf16(conv) + addend), like an eager add kernel; !has: the row keeps its bits (compact stream: even pixels only)
+__device__ __forceinline__ void cv_row_add(uint32_t (&cw)[4], const cv_u32x4 aw, bool has) {
+#pragma unroll
+    for (int q2 = 0; q2 < 4; ++q2) {
+        const uint32_t sum = cv_pack_bf16(cv_bf_lo(cw[q2]) + cv_bf_lo(aw[q2]), cv_bf_hi(cw[q2]) + cv_bf_hi(aw[q2]));
+        cw[q2] = has ? sum : cw[q2];
+    }
+}
+// ReLU backward of the tensor this gradient belongs to: zero where !(mask > 0)
+__device__ __forceinline__ void cv_row_mask(uint32_t (&cw)[4], const cv_u32x4 kw) {
+#pragma unroll
+    for (int q2 = 0; q2 < 4; ++q2) {
+        if (!(cv_bf_lo(kw[q2]) > 0.0f)) cw[q2] &= 0xffff0000u;
+        if (!(cv_bf_hi(kw[q2]) > 0.0f)) cw[q2] &= 0x0000ffffu;
+    }
+}
+// the same decision, from the forward's bit per element (bit j of bb = channel j of the chunk)
+__device__ __forceinline__ void cv_row_mask_bits(uint32_t (&cw)[4], uint32_t bb) {
+#pragma unroll
+    for (int q2 = 0; q2 < 4; ++q2) {
+        if (!(bb & (1u << (2 * q2)))) cw[q2] &= 0xffff0000u;
+        if (!(bb & (2u << (2 * q2)))) cw[q2] &= 0x0000ffffu;
+    }
+}
+// fused BatchNorm-backward partials: (sum g, sum g * bnx) of the gradient as stored; relu: g under the recomputed mask bnx * maf + mbf > 0
+__device__ __forceinline__ void cv_row_bn_sums(const uint32_t (&cw)[4], const cv_u32x4 xw, bool relu, const float (&maf)[8], const float (&mbf)[8],
+                                               float (&ssum)[8], float (&ssq)[8]) {
+#pragma unroll
+    for (int q2 = 0; q2 < 4; ++q2) {
+        float g0 = cv_bf_lo(cw[q2]), g1 = cv_bf_hi(cw[q2]);
+        const float x0 = cv_bf_lo(xw[q2]), x1 = cv_bf_hi(xw[q2]);
+        if (relu) {
+            if (!(x0 * maf[2 * q2] + mbf[2 * q2] > 0.0f)) g0 = 0.0f;
+            if (!(x1 * maf[2 * q2 + 1] + mbf[2 * q2 + 1] > 0.0f)) g1 = 0.0f;
+        }
+        ssum[2 * q2] += g0; ssq[2 * q2] += g0 * x0; ssum[2 * q2 + 1] += g1; ssq[2 * q2 + 1] += g1 * x1;
+    }
+}
+
 // LEAN: the launch has no fused operand (no addend / compact addend / ReLU mask / BatchNorm-backward sums, dense rows): the plain
 // forward. Those code paths then do not exist in the kernel, which brings its register count under 128 = a fourth wavefront per SIMD.
 // cv_epilogue_staged: everything after the accumulators have been written to the staging tile Cs = smem [128 pixels][BN * 2 + 16 bytes] (by
@@ -67,11 +121,7 @@ __device__ __forceinline__ void cv_epilogue_staged(const ConvP& p, unsigned char
                 const uint4 c = *reinterpret_cast<const uint4*>(cs + i * RPI * CS_STRIDE);
                 if (p.stats) {
                     const uint32_t sw[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        const float f0 = __uint_as_float(sw[q2] << 16), f1 = __uint_as_float(sw[q2] & 0xffff0000u);
-                        ssum[2 * q2] += f0; ssq[2 * q2] += f0 * f0; ssum[2 * q2 + 1] += f1; ssq[2 * q2 + 1] += f1 * f1;
-                    }
+                    cv_row_fwd_stats(sw, ssum, ssq);
                 }
                 // `sc1 nt`: written through to the memory side (where the 256 MB Infinity Cache keeps it for the BatchNorm pass that reads it
                 // next) and streamed past the L2, whose lines are better spent on the operands the neighbouring tiles share. Same-box A/B,
@@ -135,10 +185,8 @@ __device__ __forceinline__ void cv_epilogue_staged(const ConvP& p, unsigned char
             uint32_t ob = gob + (uint32_t)((hh_) * HALF + ii) * gsb, oa = ob;                                   \
             if (decode) {                                         /* (arithmetic only: no memory instruction inside) */ \
                 const int m = m0 + srow + ((hh_) * HALF + ii) * RPI;                                            \
-                int q1 = (int)((float)m * p.inv_wo), wo = m - q1 * p.Wo;                                        \
-                if (wo < 0) { --q1; wo += p.Wo; } else if (wo >= p.Wo) { ++q1; wo -= p.Wo; }                    \
-                int n = (int)((float)q1 * p.inv_ho), ho = q1 - n * p.Ho;                                        \
-                if (ho < 0) { --n; ho += p.Ho; } else if (ho >= p.Ho) { ++n; ho -= p.Ho; }                      \
+                int n, ho, wo;                                                                                  \
+                cv_pixel_decode(m, p.Wo, p.Ho, p.inv_wo, p.inv_ho, n, ho, wo);                                  \
                 const bool valid = full || m < p.M;                                                             \
                 if (p.o2) {                                        /* parity class of a stride-2 data gradient: scattered rows */ \
                     ob = valid ? (uint32_t)((((size_t)n * p.OH + 2 * ho + p.o_a) * p.OW + 2 * wo + p.o_b) * p.Cout + n0 + sch * 8) * 2u : (uint32_t)CV_OOB; \
@@ -167,53 +215,13 @@ __device__ __forceinline__ void cv_epilogue_staged(const ConvP& p, unsigned char
                 const cv_u32x4 cc = *reinterpret_cast<const cv_u32x4*>(cs + i * RPI * CS_STRIDE);
                 uint32_t cw[4] = {cc.x, cc.y, cc.z, cc.w};
                 if (!full && !(m0 + srow + i * RPI < p.M)) cw[0] = cw[1] = cw[2] = cw[3] = 0u;   // (not stored; zeros in the sums)
-                if (fwd_stats) {
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        const float f0 = __uint_as_float(cw[q2] << 16), f1 = __uint_as_float(cw[q2] & 0xffff0000u);
-                        ssum[2 * q2] += f0; ssq[2 * q2] += f0 * f0; ssum[2 * q2 + 1] += f1; ssq[2 * q2 + 1] += f1 * f1;
-                    }
-                }
-                if (addp) {                                     // y = bf16(bf16(conv) + addend), like an eager add kernel
-                    const uint32_t aw[4] = {f_add[set][ii].x, f_add[set][ii].y, f_add[set][ii].z, f_add[set][ii].w};
-                    const bool has = p.addend || f_oa[set][ii] != (uint32_t)CV_OOB;   // (compact stream: even pixels only; the others keep their bits)
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        const uint32_t sum = cv_pack_bf16(__uint_as_float(cw[q2] << 16) + __uint_as_float(aw[q2] << 16),
-                                                          __uint_as_float(cw[q2] & 0xffff0000u) + __uint_as_float(aw[q2] & 0xffff0000u));
-                        cw[q2] = has ? sum : cw[q2];
-                    }
-                }
-                if (p.mask) {                                   // ReLU backward of the tensor this gradient belongs to
-                    const uint32_t kw[4] = {f_mask[set][ii].x, f_mask[set][ii].y, f_mask[set][ii].z, f_mask[set][ii].w};
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        if (!(__uint_as_float(kw[q2] << 16) > 0.0f)) cw[q2] &= 0xffff0000u;
-                        if (!(__uint_as_float(kw[q2] & 0xffff0000u) > 0.0f)) cw[q2] &= 0x0000ffffu;
-                    }
-                }
-                if (p.mask_bits) {                              // the same decision, from the forward's bit per element
-                    const uint32_t bb = f_bits[set][ii];
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        if (!(bb & (1u << (2 * q2)))) cw[q2] &= 0xffff0000u;
-                        if (!(bb & (2u << (2 * q2)))) cw[q2] &= 0x0000ffffu;
-                    }
-                }
+                if (fwd_stats) cv_row_fwd_stats(cw, ssum, ssq);
+                // (compact stream: rows at even pixels only; the others keep their bits)
+                if (addp) cv_row_add(cw, f_add[set][ii], p.addend || f_oa[set][ii] != (uint32_t)CV_OOB);
+                if (p.mask) cv_row_mask(cw, f_mask[set][ii]);
+                if (p.mask_bits) cv_row_mask_bits(cw, f_bits[set][ii]);
                 __builtin_amdgcn_raw_buffer_store_b128(cv_u32x4{cw[0], cw[1], cw[2], cw[3]}, r_y, (int)f_ob[set][ii], 0, 2);   // (aux 2 = non-temporal, as above: -0.14 ms)
-                if (p.bnx) {
-                    const uint32_t xw[4] = {f_bnx[set][ii].x, f_bnx[set][ii].y, f_bnx[set][ii].z, f_bnx[set][ii].w};
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        float g0 = __uint_as_float(cw[q2] << 16), g1 = __uint_as_float(cw[q2] & 0xffff0000u);
-                        const float x0 = __uint_as_float(xw[q2] << 16), x1 = __uint_as_float(xw[q2] & 0xffff0000u);
-                        if (p.bn_gamma) {
-                            if (!(x0 * maf[2 * q2] + mbf[2 * q2] > 0.0f)) g0 = 0.0f;
-                            if (!(x1 * maf[2 * q2 + 1] + mbf[2 * q2 + 1] > 0.0f)) g1 = 0.0f;
-                        }
-                        ssum[2 * q2] += g0; ssq[2 * q2] += g0 * x0; ssum[2 * q2 + 1] += g1; ssq[2 * q2 + 1] += g1 * x1;
-                    }
-                }
+                if (p.bnx) cv_row_bn_sums(cw, f_bnx[set][ii], p.bn_gamma != nullptr, maf, mbf, ssum, ssq);
             }
         }
 #undef CV_EPI_LOAD
@@ -241,10 +249,8 @@ __device__ __forceinline__ void cv_epilogue_staged(const ConvP& p, unsigned char
             if (full || m0 + srow + i * RPI < p.M) {
                 if (decode) {
                     const int m = m0 + srow + i * RPI;
-                    int q1 = (int)((float)m * p.inv_wo), wo = m - q1 * p.Wo;
-                    if (wo < 0) { --q1; wo += p.Wo; } else if (wo >= p.Wo) { ++q1; wo -= p.Wo; }
-                    int n = (int)((float)q1 * p.inv_ho), ho = q1 - n * p.Ho;
-                    if (ho < 0) { --n; ho += p.Ho; } else if (ho >= p.Ho) { ++n; ho -= p.Ho; }
+                    int n, ho, wo;
+                    cv_pixel_decode(m, p.Wo, p.Ho, p.inv_wo, p.inv_ho, n, ho, wo);
                     if (p.o2)                                    // parity class of a stride-2 data gradient: scattered rows
                         orow[ii] = (uint32_t)((((size_t)n * p.OH + 2 * ho + p.o_a) * p.OW + 2 * wo + p.o_b) * p.Cout + n0 + sch * 8);
                     if (p.addend2 && !((ho | wo) & 1))           // rows at even (ho, wo) also receive compact[n, ho/2, wo/2, :]
@@ -261,68 +267,16 @@ __device__ __forceinline__ void cv_epilogue_staged(const ConvP& p, unsigned char
         for (int ii = 0; ii < HALF; ++ii) {
             const int i = hh * HALF + ii;
             if (full || m0 + srow + i * RPI < p.M) {
-                uint4 c = *reinterpret_cast<const uint4*>(cs + i * RPI * CS_STRIDE);
-                if (fwd_stats) {
-                    const uint32_t sw[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        const float f0 = __uint_as_float(sw[q2] << 16), f1 = __uint_as_float(sw[q2] & 0xffff0000u);
-                        ssum[2 * q2] += f0; ssq[2 * q2] += f0 * f0; ssum[2 * q2 + 1] += f1; ssq[2 * q2 + 1] += f1 * f1;
-                    }
-                }
-                if (p.addend) {                                 // y = bf16(bf16(conv) + addend), like an eager add kernel
-                    uint32_t cw[4] = {c.x, c.y, c.z, c.w};
-                    const uint32_t aw[4] = {v_add[ii].x, v_add[ii].y, v_add[ii].z, v_add[ii].w};
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2)
-                        cw[q2] = cv_pack_bf16(__uint_as_float(cw[q2] << 16) + __uint_as_float(aw[q2] << 16),
-                                              __uint_as_float(cw[q2] & 0xffff0000u) + __uint_as_float(aw[q2] & 0xffff0000u));
-                    c = make_uint4(cw[0], cw[1], cw[2], cw[3]);
-                }
-                if (p.addend2 && o2row[ii] != ~0u) {            // (three launches per step: loaded here, not ahead)
-                    const uint4 a = *reinterpret_cast<const uint4*>(p.addend2 + o2row[ii]);
-                    uint32_t cw[4] = {c.x, c.y, c.z, c.w};
-                    const uint32_t aw[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2)
-                        cw[q2] = cv_pack_bf16(__uint_as_float(cw[q2] << 16) + __uint_as_float(aw[q2] << 16),
-                                              __uint_as_float(cw[q2] & 0xffff0000u) + __uint_as_float(aw[q2] & 0xffff0000u));
-                    c = make_uint4(cw[0], cw[1], cw[2], cw[3]);
-                }
-                if (p.mask) {                                   // ReLU backward of the tensor this gradient belongs to
-                    const uint32_t kw[4] = {v_mask[ii].x, v_mask[ii].y, v_mask[ii].z, v_mask[ii].w};
-                    uint32_t cw[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        if (!(__uint_as_float(kw[q2] << 16) > 0.0f)) cw[q2] &= 0xffff0000u;
-                        if (!(__uint_as_float(kw[q2] & 0xffff0000u) > 0.0f)) cw[q2] &= 0x0000ffffu;
-                    }
-                    c = make_uint4(cw[0], cw[1], cw[2], cw[3]);
-                }
-                if (p.mask_bits) {                              // the same decision, from the forward's bit per element
-                    uint32_t cw[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        if (!(v_bits[ii] & (1u << (2 * q2)))) cw[q2] &= 0xffff0000u;
-                        if (!(v_bits[ii] & (2u << (2 * q2)))) cw[q2] &= 0x0000ffffu;
-                    }
-                    c = make_uint4(cw[0], cw[1], cw[2], cw[3]);
-                }
-                __builtin_nontemporal_store(cv_u32x4{c.x, c.y, c.z, c.w}, reinterpret_cast<cv_u32x4*>(p.y + orow[ii]));
-                if (p.bnx) {
-                    const uint32_t gw[4] = {c.x, c.y, c.z, c.w};
-                    const uint32_t xw[4] = {v_bnx[ii].x, v_bnx[ii].y, v_bnx[ii].z, v_bnx[ii].w};
-#pragma unroll
-                    for (int q2 = 0; q2 < 4; ++q2) {
-                        float g0 = __uint_as_float(gw[q2] << 16), g1 = __uint_as_float(gw[q2] & 0xffff0000u);
-                        const float x0 = __uint_as_float(xw[q2] << 16), x1 = __uint_as_float(xw[q2] & 0xffff0000u);
-                        if (p.bn_gamma) {
-                            if (!(x0 * maf[2 * q2] + mbf[2 * q2] > 0.0f)) g0 = 0.0f;
-                            if (!(x1 * maf[2 * q2 + 1] + mbf[2 * q2 + 1] > 0.0f)) g1 = 0.0f;
-                        }
-                        ssum[2 * q2] += g0; ssq[2 * q2] += g0 * x0; ssum[2 * q2 + 1] += g1; ssq[2 * q2 + 1] += g1 * x1;
-                    }
-                }
+                const uint4 c = *reinterpret_cast<const uint4*>(cs + i * RPI * CS_STRIDE);
+                uint32_t cw[4] = {c.x, c.y, c.z, c.w};
+                if (fwd_stats) cv_row_fwd_stats(cw, ssum, ssq);
+                if (p.addend) cv_row_add(cw, cv_vec(v_add[ii]), true);
+                if (p.addend2 && o2row[ii] != ~0u)              // (three launches per step: loaded here, not ahead)
+                    cv_row_add(cw, cv_vec(*reinterpret_cast<const uint4*>(p.addend2 + o2row[ii])), true);
+                if (p.mask) cv_row_mask(cw, cv_vec(v_mask[ii]));
+                if (p.mask_bits) cv_row_mask_bits(cw, v_bits[ii]);
+                __builtin_nontemporal_store(cv_u32x4{cw[0], cw[1], cw[2], cw[3]}, reinterpret_cast<cv_u32x4*>(p.y + orow[ii]));
+                if (p.bnx) cv_row_bn_sums(cw, cv_vec(v_bnx[ii]), p.bn_gamma != nullptr, maf, mbf, ssum, ssq);
             }
         }
     }

@@ -299,11 +299,7 @@ __global__ void __launch_bounds__(DIR_TPB) __attribute__((amdgpu_waves_per_eu(FT
     constexpr int NS = ARITH ? FT_SPLIT_STAGES : 2;                 // LDS stages: two for the exact arithmetic (bound by the matrix pipe), a ring for the split ones
     constexpr int LDS_BYTES = (NS * STAGE > 64 * TN * 4) ? NS * STAGE : 64 * TN * 4;   // the K-loop stages; the epilogue's 64-row slab
     __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
-    int lin;
-    {
-        const int b = blockIdx.x, n8 = q.nblocks / 8, r8 = q.nblocks % 8, xcd = b % 8, i = b / 8;
-        lin = (xcd < r8 ? xcd * (n8 + 1) : r8 * (n8 + 1) + (xcd - r8) * n8) + i;
-    }
+    const int lin = cv_xcd_tile(blockIdx.x, q.nblocks);
     const int mt = lin / q.ntn, nt = lin - mt * q.ntn;
     const int m0 = mt * TM, n0 = nt * TN;
     const int t = threadIdx.x, lane = t & 63;
@@ -409,10 +405,8 @@ __global__ void __launch_bounds__(DIR_TPB) __attribute__((amdgpu_waves_per_eu(FT
             } else {
                 const int k = k0 + b_kr[i];
                 if (k < kend && b_col[i] < p.Ncol) {
-                    int q1 = (int)((float)k * q.inv_wo), wo = k - q1 * p.Wo;
-                    if (wo < 0) { --q1; wo += p.Wo; } else if (wo >= p.Wo) { ++q1; wo -= p.Wo; }
-                    int img = (int)((float)q1 * q.inv_ho), ho = q1 - img * p.Ho;
-                    if (ho < 0) { --img; ho += p.Ho; } else if (ho >= p.Ho) { ++img; ho -= p.Ho; }
+                    int img, ho, wo;
+                    cv_pixel_decode(k, p.Wo, p.Ho, q.inv_wo, q.inv_ho, img, ho, wo);
                     const int hi = ho * p.stride - p.pad + b_r[i], wi = wo * p.stride - p.pad + b_s[i];
                     if ((unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W) off = ((((img * p.H + hi) * p.W + wi) * p.Cin) + b_ci[i]) * 4;
                 }

@@ -1,6 +1,8 @@
-// Shared pieces of the MFMA implicit-GEMM convolution kernels (dir_conv.hip): launch parameters, tile constants, bf16 packing, accumulator staging, inline-asm LDS-DMA.
+// Shared pieces of the MFMA implicit-GEMM convolution kernels (dir_conv.hip): launch parameters, tile constants, the A-row origin of the
+// K-loop loaders, buffer descriptors, bf16 packing, accumulator staging, inline-asm LDS-DMA. (Tile remap and pixel decode: dir_conv_index.h.)
 #pragma once
 #include "dir_common.h"
+#include "dir_conv_index.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -31,6 +33,42 @@ struct ConvBn { const void* x; const float* gamma; const float* beta; const floa
 constexpr int CV_BM = 128, CV_BK = 64, CV_ROWB = CV_BK * 2;      // 128-byte LDS rows
 constexpr int CV_DMA_MIN_KT = 32;                                // shortest K loop (64-wide steps) that takes the LDS-DMA variant: measured +3...+20 % from 32 steps up, mixed at 16, slower below (profiles/r02_conv_variants.txt)
 constexpr int CV_OOB = (int)0x80000000;                         // buffer-load offset beyond any tensor: the load returns zeros
+
+// A-operand row of the forward K loops: for GEMM row m and the lane's 16-byte chunk, the signed byte offset of the row's (hi0, wi0) pixel
+// in x and a bit per filter tap that falls inside the image. Everything position dependent is computed ONCE here; per K-step the kernels
+// add a wave-uniform tap offset and send out-of-image taps out of the buffer's range (the load returns zeros: no masking instructions).
+// Rows past M keep amask = 0 (every tap out of range).
+__device__ __forceinline__ void cv_row_origin(const ConvP& p, int m, int chunk, int& aoff, uint32_t& amask) {
+    aoff = 0; amask = 0;
+    if (m >= p.M) return;
+    if (p.simple) { aoff = (m * p.Cin + chunk * 8) * 2; amask = 1u; return; }
+    int n, ho, wo;
+    cv_pixel_decode(m, p.Wo, p.Ho, p.inv_wo, p.inv_ho, n, ho, wo);
+    const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
+    aoff = (((n * p.H + hi0) * p.W + wi0) * p.Cin + chunk * 8) * 2;
+    for (int r = 0; r < p.R; ++r)
+        for (int s2 = 0; s2 < p.S; ++s2)
+            if ((unsigned)(hi0 + r) < (unsigned)p.H && (unsigned)(wi0 + s2) < (unsigned)p.W) amask |= 1u << (r * p.S + s2);
+}
+
+// Raw-buffer descriptors of the two K-loop operands: x [N][H][W][Cin] and the weight matrix [Cout][K], K = KT * CV_BK, both bf16.
+// Offsets beyond the extent (CV_OOB) read zeros.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t cv_rsrc_x(const ConvP& p) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.x), (short)0, (int)((unsigned)(p.N * p.H * p.W) * (unsigned)p.Cin * 2u), 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t cv_rsrc_w(const ConvP& p, int K) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.w), (short)0, (int)((unsigned)p.Cout * (unsigned)K * 2u), 0x00020000);
+}
+
+template <int MI, int NI>
+__device__ __forceinline__ void cv_zero_acc(f32x16 (&acc)[MI][NI]) {
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.0f;
+}
 
 __device__ __forceinline__ uint32_t cv_f2bf(float f) {
     uint32_t u = __float_as_uint(f);

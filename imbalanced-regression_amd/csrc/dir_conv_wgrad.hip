@@ -18,6 +18,7 @@
 // no atomics, no zero-fill pass.
 #include <cstdlib>
 #include "dir_common.h"
+#include "dir_conv_index.h"
 
 namespace {
 
@@ -95,11 +96,7 @@ conv_wgrad_kernel(WgP p) {
     // Workgroup order: filter tap fastest, then ci tile, co tile, K range — workgroups that re-read the same dY rows
     // (all taps / ci tiles of one (co tile, K range)) and overlapping X rows (neighbouring taps) are adjacent, and
     // the XCD remap keeps adjacent ids on one XCD so those re-reads hit that XCD's L2.
-    int b;
-    {
-        const int nb = gridDim.x, id = blockIdx.x, q = nb / 8, r = nb % 8, xcd = id % 8, i = id / 8;
-        b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    int b = cv_xcd_tile(blockIdx.x, gridDim.x);
     const int tap = b % p.RS; b /= p.RS;
     const int tn = b % p.tiles_n; b /= p.tiles_n;
     const int tm = b % p.tiles_m; b /= p.tiles_m;
@@ -157,10 +154,8 @@ conv_wgrad_kernel(WgP p) {
     WgWalk walk = {0, 0, 0, 0};
     if (!SIMPLE && doB) {                                       // decode the first row of this thread once
         const int mm = ks0 * WG_BK + 4 * gb;
-        int q1 = (int)((float)mm * p.inv_wo); int wo = mm - q1 * p.Wo;
-        if (wo < 0) { --q1; wo += p.Wo; } else if (wo >= p.Wo) { ++q1; wo -= p.Wo; }
-        int n = (int)((float)q1 * p.inv_ho); int ho = q1 - n * p.Ho;
-        if (ho < 0) { --n; ho += p.Ho; } else if (ho >= p.Ho) { ++n; ho -= p.Ho; }
+        int n, ho, wo;
+        cv_pixel_decode(mm, p.Wo, p.Ho, p.inv_wo, p.inv_ho, n, ho, wo);
         walk.n = n; walk.hs = ho * p.stride; walk.ws = wo * p.stride;
         walk.off = (((n * p.H + walk.hs + trp) * p.W + walk.ws + tsp) * p.Cin + ci0 + cb * 8) * 2;
     }
@@ -334,11 +329,7 @@ template <int NST>
 __global__ void __launch_bounds__(DIR_TPB) __attribute__((amdgpu_waves_per_eu(NST == 1 ? 4 : 2)))
 conv_wgrad1_dma_kernel(WgP p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int b;
-    {
-        const int nb = gridDim.x, id = blockIdx.x, q = nb / 8, r = nb % 8, xcd = id % 8, i = id / 8;
-        b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
-    }
+    int b = cv_xcd_tile(blockIdx.x, gridDim.x);
     const int tn = b % p.tiles_n; b /= p.tiles_n;
     const int tm = b % p.tiles_m; b /= p.tiles_m;
     const int split = b;

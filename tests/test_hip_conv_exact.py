@@ -167,6 +167,13 @@ FWD_CASES = [  # (N, Cin, H, W, Cout, k, stride, pad, variant, kernel the plan m
     ((7, 64, 5, 3, 192, 3, 2, 1), V.CONV_AUTO, "Cout 192 (three 64-wide tiles)"),
     ((2, 256, 56, 56, 512, 1, 2, 0), V.CONV_AUTO, "1x1 stride 2"), ((1, 1024, 14, 14, 2048, 1, 2, 0), V.CONV_TILE_REG, "1x1 stride 2 reg"),
     ((2, 512, 7, 7, 512, 3, 1, 1), V.CONV_TILE_REG, "reg<128,2,2> 7x7"), ((2, 512, 7, 7, 512, 3, 1, 1), V.CONV_TILE_DMA, "dma 7x7"),
+    # the smallest shapes that still reach a branch of the shared prologue / epilogue: one ragged tile (M = 49) through the LEAN and the
+    # pipelined store loops, one 256 x 256 CU tile (M = 256), one or two images through every patch-staged instantiation
+    ((1, 64, 7, 7, 64, 3, 1, 1), V.CONV_AUTO, "reg<64,1,1> lean, M = 49"), ((1, 64, 7, 7, 64, 3, 1, 1), V.CONV_TILE_DMA, "dma<64>, M = 49"),
+    ((1, 64, 7, 7, 128, 1, 1, 0), V.CONV_AUTO, "single DMA lean, M = 49"), ((1, 64, 16, 16, 256, 3, 1, 1), V.CONV_BIG, "big lean, one tile"),
+    ((2, 64, 14, 14, 64, 3, 1, 1), V.CONV_PATCH3, "patch<14,64> N=2"), ((2, 64, 14, 14, 128, 3, 1, 1), V.CONV_PATCH3, "patch<14,128> N=2"),
+    ((1, 64, 28, 28, 64, 3, 1, 1), V.CONV_PATCH3, "patch<28,64> N=1"), ((1, 64, 28, 28, 128, 3, 1, 1), V.CONV_PATCH3, "patch<28,128> N=1"),
+    ((1, 64, 56, 56, 64, 3, 1, 1), V.CONV_PATCH3, "patch<56,64> N=1"), ((1, 64, 56, 56, 128, 3, 1, 1), V.CONV_PATCH3, "patch<56,128> N=1"),
 ]
 
 
@@ -266,6 +273,19 @@ DGRAD_CASES = [  # (N, Cy, H, W, Cx, k, variant, operands)   Cy = channels of dy
     ((3, 128, 12, 12, 128, 1), V.CONV_AUTO, "s2"), ((3, 128, 12, 12, 128, 1), V.CONV_TILE_REG, "s2+mask"),
     ((3, 128, 12, 10, 64, 1), V.CONV_AUTO, "s2+bits+bnx"), ((3, 128, 12, 12, 128, 1), V.CONV_AUTO, "addend+s2+mask"),
     ((5, 512, 7, 7, 512, 3), V.CONV_AUTO, "addend+mask"), ((2, 2048, 7, 7, 128, 1), V.CONV_AUTO, "addend+bits+bnx"),
+    # (kernel form x epilogue option) pairs the cases above do not reach, at the smallest shapes that do. The both-addends loop
+    # (addend+s2) with the bit mask, the BatchNorm sums with and without gamma, on 64-wide tiles and under the register-staged
+    # (one- and two-tile prefetch), two-stage LDS-DMA and patch-staged K loops:
+    ((2, 64, 8, 8, 64, 1), V.CONV_AUTO, "addend+s2+bits+bnx+recompute"), ((2, 64, 8, 8, 64, 3), V.CONV_TILE_REG, "addend+s2+mask+bnx"),
+    ((2, 256, 8, 8, 64, 3), V.CONV_TILE_REG, "addend+s2+bits"), ((2, 256, 8, 8, 128, 3), V.CONV_TILE_DMA, "addend+s2+mask+bnx+recompute"),
+    ((1, 64, 56, 56, 128, 3), V.CONV_PATCH3, "addend+s2+mask"),
+    # the pipelined loop: a ragged single tile (M = 49), the 256 x 256 CU tile with the mask tensor / the compact addend, the patch-staged
+    # kernel with the addends and the bit mask, the two-stage LDS-DMA and two-tile-prefetch loops with the compact addend
+    ((1, 64, 7, 7, 64, 1), V.CONV_AUTO, "addend+mask+bnx"), ((1, 64, 7, 7, 128, 3), V.CONV_TILE_DMA, "bits+bnx+recompute"),
+    ((1, 64, 16, 16, 256, 3), V.CONV_BIG, "mask+bnx"), ((1, 64, 16, 16, 256, 3), V.CONV_BIG, "s2+bits"),
+    ((2, 64, 14, 14, 128, 3), V.CONV_PATCH3, "addend+bits"), ((1, 64, 28, 28, 64, 3), V.CONV_PATCH3, "s2+bnx"),
+    ((2, 256, 8, 8, 128, 3), V.CONV_TILE_DMA, "s2+bnx+recompute"), ((2, 256, 8, 8, 128, 3), V.CONV_TILE_REG, "s2+mask"),
+    ((2, 64, 8, 8, 128, 1), V.CONV_AUTO, "bits+bnx"),
 ]
 
 

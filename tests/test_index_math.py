@@ -4,7 +4,7 @@ convolutions in float64. They pin the formulas (not the kernels — those are co
   * the incremental im2col walk of the weight-gradient kernel (csrc/dir_conv_wgrad.hip: WgWalk / wg_advance and the
     constants dir_conv_wgrad() derives) against a direct (n, ho, wo) decode, for ordinary and degenerate geometries;
   * the decomposition of a 3x3 / stride-2 / pad-1 data gradient into four stride-1 convolutions by output-pixel parity,
-    with the class-packed weight layout of conv_prep_rot_index (csrc/dir_conv.hip), against autograd;
+    with the class-packed weight layout of conv_prep_rot_index (csrc/dir_optim.hip), against autograd;
   * the compact stride-2 1x1 gradient added at the even pixels (dir_conv_dgrad_join) against autograd;
   * the 24-element row windows and packed weights of the stem kernels (csrc/dir_stem.hip), forward and weight gradient;
   * the LDS image of the all-taps 3x3 weight gradient (csrc/dir_conv_wgrad3.hip): DMA piece -> (row, physical chunk) with the
