@@ -4,7 +4,8 @@
 ``step()`` runs ONE hand-written HIP launch for all parameter tensors (``dir_adam_step``: torch's single-tensor Adam arithmetic) and
 rewrites, in the same pass, the bf16 operands of every convolution weight the MFMA kernels will read in the next forward / data
 gradient — the work of torch's multi-tensor fused Adam (5 launches) + ``dir_conv_prep_weights_batched`` before. Anything the
-kernel does not take (amsgrad, maximize, CPU / non-float32 / non-dense parameters, a differentiable step) goes to
+kernel does not take (amsgrad, maximize, CPU / non-float32 / non-dense parameters, a differentiable step, parameters of one group
+that do not share one step count) goes to
 ``torch.optim.Adam``'s own ``step`` — there is no silent change of arithmetic.
 """
 import torch
@@ -29,6 +30,7 @@ class Adam(torch.optim.Adam):
         if isinstance(group["lr"], torch.Tensor):
             return False
         dev = params[0].device
+        steps = set()
         for p in params:
             g = p.grad
             if not (p.is_cuda and p.device == dev and p.dtype == torch.float32 and g.dtype == torch.float32 and not g.is_sparse):
@@ -36,6 +38,12 @@ class Adam(torch.optim.Adam):
             if p.stride() != g.stride() or not (p.is_contiguous() or (p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last))):
                 return False
             st = self.state.get(p)
+            # one launch = one step count (the bias corrections are launch arguments). A group whose parameters do not share one —
+            # e.g. a parameter whose gradient was None for some steps, so it has no state yet next to parameters that do — is
+            # torch's loop's business
+            steps.add(float(st["step"]) if st else None)
+            if len(steps) > 1:
+                return False
             if st:                                                          # the kernel walks param, grad and both moments with ONE linear index
                 for k in ("exp_avg", "exp_avg_sq"):
                     t = st.get(k)
@@ -83,7 +91,6 @@ class Adam(torch.optim.Adam):
             params = [p for p in group["params"] if p.grad is not None]
             if not params:
                 continue
-            step = None
             for p in params:
                 st = self.state[p]
                 if len(st) == 0:                                            # torch's lazy state initialisation (adam.py: _init_group)
@@ -91,11 +98,7 @@ class Adam(torch.optim.Adam):
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["step"] += 1
-                s = int(st["step"])
-                if step is None:
-                    step = s
-                elif s != step:
-                    raise L.DirHipError("dirhip.optim.Adam: parameters of one group with different step counts")
+            step = int(self.state[params[0]]["step"])                       # the same for every parameter of the group (_ours)
             dev = params[0].device
             key = (_conv.registry_size(dev),) + tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr()) for p in params)
             cached = self._tables.get(gi)
