@@ -1,0 +1,134 @@
+// NYUD2-DIR training loss (nyud2-dir/train.py:200, `loss = torch.mean(((output - depth) ** 2) * weight)`) with the per-pixel LDS weight
+// of nyud2-dir/loaddata.py:57-69 (`bucket_weights[min(int(d * 10), 99)]`) looked up in the same pass: value and gradient in ONE
+// streaming launch plus a one-workgroup fold.  The reference builds the weight map on the host with a Python `map` over every pixel;
+// here the bucket table sits in LDS and the weight map is never written.
+//
+// Per pixel, float32, one rounding per operation (-ffp-contract=off):
+//   b  = clamp(int(depth * mult), 0, bucket_num - 1)        float32 product, truncated: dir_fds_bin_scaled with bucket_start 0
+//   w  = table[b]   (1 when there is no table, and 1 for a NaN depth)
+//   d  = pred - depth;   t = (d * d) * w;   dx = ((1 / n) * w) * (2 * d)      torch's autograd order: mean, mul, pow backward
+// A negative depth goes to bucket 0 (as PixelWeights does); the reference's Python list would wrap a negative index.  NaN propagates.
+//
+// Reduction, bit-reproducible (no float atomics anywhere):
+//   thread   float64 running sum over its pixels in index order (one aligned 16-byte quad per step, edge quads element-wise)
+//   wave     64-lane butterfly in float64
+//   block    the four wave sums added in wave order -> one float64 partial in the workspace
+//   fold     a second launch of one workgroup adds the partials in workgroup order, divides by n in float64, rounds to float32
+#include "dir_common.h"
+
+#define DLOSS_MAX_BUCKETS 256                 // LDS: one float per bucket
+#define DLOSS_MAX_BLOCKS 256                  // one per CU; bounds the partial buffer (2 KB) and the serial fold
+
+static int dloss_grid(long long n) {
+    const long long quads = (n + 3 + 3) / 4;  // the quad grid is anchored at the 16-byte boundary below `depth`: up to 3 slots of lead-in
+    long long g = (quads + DIR_TPB - 1) / DIR_TPB;
+    if (g > DLOSS_MAX_BLOCKS) g = DLOSS_MAX_BLOCKS;
+    return g < 1 ? 1 : (int)g;
+}
+
+// min(int(depth * mult), bucket_num - 1), never below 0; the float32 product truncated (as eval_bucket of dir_eval.hip)
+__device__ __forceinline__ int dloss_bucket(float depth, float mult, int bucket_num) {
+    const float v = depth * mult;
+    int k = (v >= 2147483520.0f) ? 2147483647 : ((v <= 0.0f) ? 0 : (int)v);
+    return k > bucket_num - 1 ? bucket_num - 1 : k;
+}
+
+// one pixel: the term (d * d) * w and the unit gradient ((1 / n) * w) * (2 * d)
+__device__ __forceinline__ void dloss_pixel(float p, float z, const float* tab, float mult, int bucket_num, float inv_n, float& t, float& g) {
+    float w = 1.0f;
+    if (tab && z == z) w = tab[dloss_bucket(z, mult, bucket_num)];
+    const float d = p - z;
+    t = (d * d) * w;
+    g = (inv_n * w) * (2.0f * d);
+}
+
+__global__ void __launch_bounds__(DIR_TPB)
+depth_loss_kernel(const float* __restrict__ pred, const float* __restrict__ depth, int n, int off, bool vec, float mult,
+                  const float* __restrict__ table, int bucket_num, float* __restrict__ dx, double* __restrict__ partials) {
+    __shared__ float tab_lds[DLOSS_MAX_BUCKETS];
+    __shared__ double sh[DIR_TPB / DIR_WAVE];
+    if (table) {
+        for (int i = threadIdx.x; i < bucket_num; i += DIR_TPB) tab_lds[i] = table[i];
+        __syncthreads();
+    }
+    const float* tab = table ? tab_lds : nullptr;
+    const float inv_n = 1.0f / (float)n;
+    const int quads = (n + off + 3) / 4;
+    double acc = 0.0;
+    for (int q = (int)blockIdx.x * DIR_TPB + (int)threadIdx.x; q < quads; q += (int)gridDim.x * DIR_TPB) {
+        const long long i0 = 4ll * q - off;                                       // may be < 0 (lead-in) or reach past n (tail)
+        if (vec && i0 >= 0 && i0 + 3 < n) {                                       // 16-byte aligned by construction of the quad grid
+            const float4 zv = *reinterpret_cast<const float4*>(depth + i0);
+            const float4 pv = *reinterpret_cast<const float4*>(pred + i0);
+            float t[4];
+            float4 g;
+            dloss_pixel(pv.x, zv.x, tab, mult, bucket_num, inv_n, t[0], g.x);
+            dloss_pixel(pv.y, zv.y, tab, mult, bucket_num, inv_n, t[1], g.y);
+            dloss_pixel(pv.z, zv.z, tab, mult, bucket_num, inv_n, t[2], g.z);
+            dloss_pixel(pv.w, zv.w, tab, mult, bucket_num, inv_n, t[3], g.w);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc += (double)t[j];                      // index order
+            if (dx) *reinterpret_cast<float4*>(dx + i0) = g;
+        } else {
+            for (int j = 0; j < 4; ++j) {
+                const long long i = i0 + j;
+                if (i < 0 || i >= n) continue;
+                float t, g;
+                dloss_pixel(pred[i], depth[i], tab, mult, bucket_num, inv_n, t, g);
+                acc += (double)t;
+                if (dx) dx[i] = g;
+            }
+        }
+    }
+    acc = dir_wave_sum(acc);
+    if ((threadIdx.x & (DIR_WAVE - 1)) == 0) sh[threadIdx.x / DIR_WAVE] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+#pragma unroll
+        for (int wv = 0; wv < DIR_TPB / DIR_WAVE; ++wv) tot += sh[wv];            // wave order
+        partials[blockIdx.x] = tot;
+    }
+}
+
+static_assert(DLOSS_MAX_BLOCKS <= DIR_TPB, "the fold stages one partial per thread");
+
+__global__ void __launch_bounds__(DIR_TPB)
+depth_loss_fold_kernel(const double* __restrict__ partials, int blocks, int n, float* __restrict__ loss) {
+    __shared__ double sh[DLOSS_MAX_BLOCKS];
+    sh[threadIdx.x] = (int)threadIdx.x < blocks ? partials[threadIdx.x] : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int g = 0; g < blocks; ++g) tot += sh[g];                            // workgroup order
+        loss[0] = (float)(tot / (double)n);
+    }
+}
+
+extern "C" size_t dir_depth_loss_workspace(long long n) {
+    if (n <= 0) return 0;
+    return dir_align_up(sizeof(double) * (size_t)dloss_grid(n), 256);
+}
+
+extern "C" int dir_depth_loss(const float* pred, const float* depth, long long n, float mult, const float* table, int bucket_num,
+                              float* loss, float* dx_unit, void* workspace, size_t workspace_bytes, dir_stream_t stream) {
+    DIR_RETURN_IF(!pred || !depth || !loss || n <= 0, DIR_EINVAL);
+    DIR_RETURN_IF(table && bucket_num <= 0, DIR_EINVAL);
+    DIR_RETURN_IF(bucket_num > DLOSS_MAX_BUCKETS || n > 2100000000LL, DIR_EUNSUPPORTED);   // 32-bit pixel indices: split the batch
+    DIR_RETURN_IF((reinterpret_cast<uintptr_t>(pred) & 3u) || (reinterpret_cast<uintptr_t>(depth) & 3u) ||
+                  (reinterpret_cast<uintptr_t>(dx_unit) & 3u) || (reinterpret_cast<uintptr_t>(workspace) & 7u), DIR_EINVAL);
+    DIR_RETURN_IF(!workspace || workspace_bytes < dir_depth_loss_workspace(n), DIR_EINVAL);
+    const int grid = dloss_grid(n);
+    // quads are anchored at the 16-byte boundary below depth[0]; 16-byte accesses when pred and dx_unit sit at the same offset from one
+    // (all three 16-byte aligned is offset 0), element-wise otherwise
+    const unsigned off = (unsigned)((reinterpret_cast<uintptr_t>(depth) >> 2) & 3u);
+    const bool vec = ((reinterpret_cast<uintptr_t>(pred) >> 2) & 3u) == off &&
+                     (!dx_unit || ((reinterpret_cast<uintptr_t>(dx_unit) >> 2) & 3u) == off);
+    double* partials = static_cast<double*>(workspace);
+    hipLaunchKernelGGL(depth_loss_kernel, dim3(grid), dim3(DIR_TPB), 0, dir_s(stream), pred, depth, (int)n, (int)off, vec, mult,
+                       table, bucket_num, dx_unit, partials);
+    DIR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(depth_loss_fold_kernel, dim3(1), dim3(DIR_TPB), 0, dir_s(stream), partials, grid, (int)n, loss);
+    DIR_LAUNCH_CHECK();
+    return DIR_OK;
+}

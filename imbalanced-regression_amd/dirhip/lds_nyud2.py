@@ -7,6 +7,7 @@ buckets, the first 7 empty), smooths it with the LDS window (``convolve1d(mode='
 the same numpy / scipy calls as the reference, so it is bit-exact by construction (the windows too). Device
 part (one weight per pixel, every batch): bucket = min(int(depth * 10), 99) by the hand-written ``dir_fds_bin_scaled``
 kernel + a table lookup, instead of the reference's Python ``map`` over 17 328 pixels per image on the host.
+``PixelWeights.loss`` goes one step further: the training loss of ``train.py:200`` with the lookup folded into the loss kernel.
 """
 import logging
 
@@ -74,8 +75,19 @@ class PixelWeights:
             return torch.ones_like(depth, dtype=torch.float32)
         if depth.dtype != torch.float32:
             raise TypeError("depth must be float32 (the reference asserts it, loaddata.py:64)")
-        if self._table is None or self._table.device != depth.device:
-            self._table = torch.tensor(np.asarray(self.bucket_weights, dtype=np.float32), device=depth.device)
         flat = depth.contiguous().view(-1)
         bins = ops.bin_scaled(flat, 10.0, 0, len(self.bucket_weights))       # clamp(int(d * 10), 0, 99), float32 product
-        return self._table[bins.long()].view(depth.shape)
+        return self._device_table(depth.device)[bins.long()].view(depth.shape)
+
+    def loss(self, output, depth):
+        """train.py:200 ``torch.mean(((output - depth) ** 2) * weights(depth))`` as one fused launch (``dirhip.loss_nyud2``): the
+        bucket lookup happens inside the loss kernel, no weight map is written."""
+        from .loss_nyud2 import weighted_depth_mse_loss
+        if self.bucket_weights is None or not depth.is_cuda:
+            return weighted_depth_mse_loss(output, depth, None)
+        return weighted_depth_mse_loss(output, depth, self._device_table(depth.device))
+
+    def _device_table(self, device):
+        if self._table is None or self._table.device != device:
+            self._table = torch.tensor(np.asarray(self.bucket_weights, dtype=np.float32), device=device)
+        return self._table

@@ -226,6 +226,36 @@ def scale_by_device_scalar(t, scalar):
     return out
 
 
+# ---- NYUD2-DIR training loss -----------------------------------------------------------------------
+_LOSS_WS = {}
+
+
+def depth_loss(pred, depth, table, mult, need_grad):
+    """pred, depth f32 device tensors of equal numel (contiguous, any shape), table [bucket_num] f32 on that device or None
+    -> (loss 0-dim f32, dx_unit of pred's shape or None). One streaming launch + a one-workgroup fold; enqueue only, no sync.
+    The 2 KB workspace is kept per (device, stream): reuse is ordered by the stream."""
+    pred = L.require_device_tensor(pred, f32, "pred")
+    depth = L.require_device_tensor(depth, f32, "depth")
+    dev = pred.device
+    if pred.numel() != depth.numel() or depth.device != dev:
+        raise ValueError(f"pred and depth must have one size and device, got {tuple(pred.shape)} / {tuple(depth.shape)}")
+    if table is not None:
+        table = L.require_device_tensor(table, f32, "table")
+        if table.device != dev or table.dim() != 1:
+            raise ValueError("table must be a 1-D tensor on pred's device")
+    n = pred.numel()
+    loss = torch.empty((), dtype=f32, device=dev)
+    dx = torch.empty_like(pred) if need_grad else None
+    nbytes = L.lib().dir_depth_loss_workspace(n)
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _LOSS_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _LOSS_WS[key] = _ws(nbytes, dev)
+    L.check(L.lib().dir_depth_loss(L.ptr(pred), L.ptr(depth), n, float(mult), L.ptr(table), table.numel() if table is not None else 0,
+                                   L.ptr(loss), L.ptr(dx), L.ptr(ws), ws.numel(), L.stream_ptr(dev)), "dir_depth_loss")
+    return loss, dx
+
+
 # ---- NYUD2-DIR evaluation -------------------------------------------------------------------------
 _EVAL_WS = {}
 

@@ -679,6 +679,30 @@ size_t dir_age_eval_workspace(long long n, int num_labels);
 int dir_age_eval_accumulate(const float* pred, const float* label, const uint8_t* valid, long long n, int num_labels,
                             double* table, void* workspace, size_t workspace_bytes, dir_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * NYUD2-DIR training loss (nyud2-dir/train.py:200 `loss = torch.mean(((output - depth) ** 2) * weight)`, the weight map of
+ * nyud2-dir/loaddata.py:57-69 `bucket_weights[min(int(d * 10), 99)]` folded in): value and gradient in one streaming launch plus
+ * a one-workgroup fold; the weight map is never written.
+ *   pred, depth [n] f32 (n = B * H * W, any 4-byte aligned pointers), table [bucket_num] f32 or NULL (reweight == 'none': weight 1),
+ *   loss [1] f32, dx_unit [n] f32 or NULL (no gradient wanted).
+ *   Per pixel, float32, one rounding per operation (no fused multiply-add):
+ *     b = clamp(int(depth * mult), 0, bucket_num - 1)   (float32 product, truncated: dir_fds_bin_scaled with bucket_start 0)
+ *     w = table[b]   (1 for a NaN depth);   d = pred - depth;   t = (d * d) * w
+ *     dx_unit = ((1 / n) * w) * (2 * d),  1 / n = 1.0f / (float)n   (torch's autograd order: mean, mul, pow backward)
+ *   A negative depth goes to bucket 0 (as dirhip.lds_nyud2.PixelWeights); the reference's Python list would wrap a negative index.
+ *   A NaN depth or prediction makes its term, its dx_unit and the loss NaN; nothing is skipped or clamped.
+ *   loss[0] = (float)(sum_i (double)t_i / (double)n).  The sum is float64 in a fixed order (per thread in index order, wavefront
+ *   butterfly, the four wave sums in wave order, one partial per workgroup in `workspace`, partials added in workgroup order by a
+ *   second launch): bit-reproducible; no float atomics.  No host synchronisation.
+ *   16-byte loads and stores when pred, depth and dx_unit sit at the same offset from a 16-byte boundary (all aligned included),
+ *   element-wise at the two ends and for every other alignment.
+ *   workspace >= dir_depth_loss_workspace(n) bytes, 8-byte aligned (0 for n <= 0).
+ *   DIR_EINVAL: NULL pred / depth / loss, n <= 0, bucket_num <= 0 with a table, workspace missing or too small.
+ *   DIR_EUNSUPPORTED: bucket_num > 256 (LDS table), n > 2.1e9 (32-bit pixel indices; split the batch). */
+size_t dir_depth_loss_workspace(long long n);
+int dir_depth_loss(const float* pred, const float* depth, long long n, float mult, const float* table, int bucket_num,
+                   float* loss, float* dx_unit, void* workspace, size_t workspace_bytes, dir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
