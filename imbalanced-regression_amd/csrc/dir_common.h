@@ -53,6 +53,18 @@ __device__ __forceinline__ double dir_wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, DIR_WAVE);
     return v;
 }
+// Sum of one double per thread over a DIR_TPB workgroup, returned to every thread: wave butterfly, one LDS slot per wave, the slots
+// added in wave order (bit-reproducible). sh holds DIR_TPB / DIR_WAVE doubles; after the trailing barrier the caller may reuse it.
+__device__ __forceinline__ double dir_block_sum(double v, double* sh) {
+    v = dir_wave_sum(v);
+    if ((threadIdx.x & (DIR_WAVE - 1)) == 0) sh[threadIdx.x / DIR_WAVE] = v;
+    __syncthreads();
+    double t = 0.0;
+#pragma unroll
+    for (int i = 0; i < DIR_TPB / DIR_WAVE; ++i) t += sh[i];
+    __syncthreads();
+    return t;
+}
 __device__ __forceinline__ uint32_t dir_wave_or(uint32_t v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, DIR_WAVE);

@@ -6,6 +6,7 @@
 // float64 register accumulators, wavefront-shuffle / ballot based grouping, no atomics on the
 // data path (bit-reproducible results), grids sized >> 256 CUs.
 #include "dir_common.h"
+#include <initializer_list>
 
 // =============================================================================================
 // K1: labels -> bins
@@ -388,6 +389,25 @@ fds_combine_kernel(const float* __restrict__ feats, int C, int nb,
     m2[o] = v > 0.0 ? v : 0.0;
 }
 
+// How the row kernels (piece sums, calibration forward / backward) walk a [rows, C] float32 matrix. 16-byte accesses need C % 4 == 0
+// and every pointer a kernel touches that way 16-byte aligned (ptrs: the caller's set); rows of C / 4 <= 128 lanes that divide the
+// workgroup are NARROW: tpr lanes per row, rpb = DIR_TPB / tpr rows per workgroup pass.
+enum FdsRowForm { FDS_ROWS_SCALAR, FDS_ROWS_VEC4, FDS_ROWS_NARROW };
+struct FdsRowLayout {
+    FdsRowForm form;
+    int tpr, rpb;
+    bool vec4() const { return form != FDS_ROWS_SCALAR; }
+    int narrow_grid(int B) const { const int g = dir_cdiv(B, rpb); return g > 16384 ? 16384 : g; }   // beyond: grid-stride over the rows
+};
+static FdsRowLayout fds_row_layout(int C, std::initializer_list<const void*> ptrs) {
+    bool vec4 = C % 4 == 0;
+    for (const void* p : ptrs) vec4 = vec4 && dir_aligned16(p);
+    if (!vec4) return {FDS_ROWS_SCALAR, 0, 0};
+    const int tpr = C / 4;
+    if (tpr <= 128 && DIR_TPB % tpr == 0) return {FDS_ROWS_NARROW, tpr, DIR_TPB / tpr};
+    return {FDS_ROWS_VEC4, 0, 0};
+}
+
 extern "C" int dir_fds_scatter_stats(const void* feats, int dtype, const int32_t* bins, int n, int C, int nb,
                                      double* count, double* mean, double* m2,
                                      void* workspace, size_t workspace_bytes, dir_stream_t stream) {
@@ -422,12 +442,11 @@ extern "C" int dir_fds_scatter_stats(const void* feats, int dtype, const int32_t
     hipLaunchKernelGGL(fds_group_place_kernel, dim3(w.ntiles), dim3(DIR_WAVE), lds_nb, s,
                        bins, n, nb, nbits, w.tile_hist, w.offsets, w.perm);
     DIR_LAUNCH_CHECK();
-    const bool vec4 = (C % 4 == 0) && dir_aligned16(feats);
-    const int tpr = C / 4;
-    if (vec4 && tpr <= 128 && DIR_TPB % tpr == 0) {
-        hipLaunchKernelGGL(fds_piece_sums_narrow_kernel, dim3(w.maxpieces), dim3(DIR_TPB), 0, s, f, C, tpr, w.perm, w.offsets,
+    const FdsRowLayout lay = fds_row_layout(C, {feats});
+    if (lay.form == FDS_ROWS_NARROW) {
+        hipLaunchKernelGGL(fds_piece_sums_narrow_kernel, dim3(w.maxpieces), dim3(DIR_TPB), 0, s, f, C, lay.tpr, w.perm, w.offsets,
                            w.npieces, w.piece_bin, w.piece_p0, w.piece_p1, w.partials);
-    } else if (vec4) {
+    } else if (lay.form == FDS_ROWS_VEC4) {
         dim3 grid(w.maxpieces, dir_cdiv(C, DIR_TPB * 4));
         hipLaunchKernelGGL(fds_piece_sums_kernel<4>, grid, dim3(DIR_TPB), 0, s, f, C, w.perm, w.offsets,
                            w.npieces, w.piece_bin, w.piece_p0, w.piece_p1, w.partials);
@@ -446,59 +465,18 @@ extern "C" int dir_fds_scatter_stats(const void* feats, int dtype, const int32_t
 // =============================================================================================
 // K3: momentum update of the running tables
 // =============================================================================================
-__global__ void __launch_bounds__(DIR_TPB)
-fds_finalize_tables_kernel(const double* __restrict__ count, const double* __restrict__ mean,
-                           const double* __restrict__ m2, int C, int factor_mode, double momentum,
-                           float* __restrict__ running_mean, float* __restrict__ running_var,
-                           const float* __restrict__ tracked) {
-    const int b = blockIdx.x;
-    const double n = count[b];
-    if (n <= 0.0) return;                                   // bin unseen this epoch: keep (fds.py loop skips it)
-    double factor;
-    if (factor_mode == DIR_FACTOR_ZERO) factor = 0.0;
-    else if (factor_mode == DIR_FACTOR_MOMENTUM) factor = momentum;
-    else factor = 1.0 - n / (double)(tracked[b] + (float)n);    // fds.py:105-106 with the bumped counter
-    const float a = (float)(1.0 - factor), f = (float)factor;
-    for (int col = blockIdx.y * DIR_TPB + threadIdx.x; col < C; col += gridDim.y * DIR_TPB) {
-        const size_t o = (size_t)b * C + col;
-        const float cm = (float)mean[o];
-        const float cv = (n == 1.0) ? 0.0f : (float)(m2[o] / (n - 1.0));   // fds.py:102
-        running_mean[o] = a * cm + f * running_mean[o];
-        running_var[o] = a * cv + f * running_var[o];
-    }
-}
-
-__global__ void fds_finalize_tracked_kernel(const double* __restrict__ count, int nb, float* __restrict__ tracked) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < nb && count[b] > 0.0) tracked[b] = tracked[b] + (float)count[b];   // fds.py:104
-}
-
-extern "C" int dir_fds_finalize_update(const double* count, const double* mean, const double* m2, int nb, int C,
-                                       int factor_mode, double momentum,
-                                       float* running_mean, float* running_var, float* num_samples_tracked,
-                                       dir_stream_t stream) {
-    DIR_RETURN_IF(!count || !mean || !m2 || !running_mean || !running_var || !num_samples_tracked, DIR_EINVAL);
-    DIR_RETURN_IF(nb <= 0 || C <= 0 || factor_mode < 0 || factor_mode > 2, DIR_EINVAL);
-    int gy = dir_cdiv(C, DIR_TPB); if (gy > 64) gy = 64;
-    hipLaunchKernelGGL(fds_finalize_tables_kernel, dim3(nb, gy), dim3(DIR_TPB), 0, dir_s(stream),
-                       count, mean, m2, C, factor_mode, momentum, running_mean, running_var, num_samples_tracked);
-    DIR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fds_finalize_tracked_kernel, dim3(dir_cdiv(nb, DIR_TPB)), dim3(DIR_TPB), 0, dir_s(stream),
-                       count, nb, num_samples_tracked);
-    DIR_LAUNCH_CHECK();
-    return DIR_OK;
-}
-
 // K3 for NON-INTEGER labels (fds.py:91-111 iterates torch.unique(labels): ONE blend per distinct label VALUE, in ascending order, into
 // bin int(value - bucket_start)). The statistics arrive per value GROUP (count / mean / m2 [U], groups sorted by value, so the groups of a bin are
 // the contiguous range bin_ptr[b] .. bin_ptr[b + 1]); a thread owns one (bin, column) and applies the bin's blends one after the other, with the
 // running num_samples_tracked the count-based factor is made from (fds.py:104-106) advancing group by group.
+// bin_ptr == nullptr is the integer-label case (fds.py:101-111): group b is the one group of bin b. A group with count 0 is skipped: the
+// bin keeps its rows (the fds.py loop never visits it).
 __global__ void __launch_bounds__(DIR_TPB)
 fds_finalize_groups_tables_kernel(const double* __restrict__ count, const double* __restrict__ mean, const double* __restrict__ m2, int C,
                                   const int32_t* __restrict__ bin_ptr, int factor_mode, double momentum,
                                   float* __restrict__ running_mean, float* __restrict__ running_var, const float* __restrict__ tracked) {
     const int b = blockIdx.x;
-    const int g0 = bin_ptr[b], g1 = bin_ptr[b + 1];
+    const int g0 = bin_ptr ? bin_ptr[b] : b, g1 = bin_ptr ? bin_ptr[b + 1] : b + 1;
     if (g0 >= g1) return;
     for (int col = blockIdx.y * DIR_TPB + threadIdx.x; col < C; col += gridDim.y * DIR_TPB) {
         const size_t ob = (size_t)b * C + col;
@@ -528,9 +506,32 @@ __global__ void fds_finalize_groups_tracked_kernel(const double* __restrict__ co
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nb) return;
     float tr = tracked[b];
-    for (int g = bin_ptr[b]; g < bin_ptr[b + 1]; ++g)
-        if (count[g] > 0.0) tr = tr + (float)count[g];
+    const int g0 = bin_ptr ? bin_ptr[b] : b, g1 = bin_ptr ? bin_ptr[b + 1] : b + 1;
+    for (int g = g0; g < g1; ++g)
+        if (count[g] > 0.0) tr = tr + (float)count[g];                     // fds.py:104
     tracked[b] = tr;
+}
+
+static int fds_finalize_launch(const double* count, const double* mean, const double* m2, int C, const int32_t* bin_ptr, int nb,
+                               int factor_mode, double momentum, float* running_mean, float* running_var, float* tracked,
+                               dir_stream_t stream) {
+    int gy = dir_cdiv(C, DIR_TPB); if (gy > 64) gy = 64;
+    hipLaunchKernelGGL(fds_finalize_groups_tables_kernel, dim3(nb, gy), dim3(DIR_TPB), 0, dir_s(stream),
+                       count, mean, m2, C, bin_ptr, factor_mode, momentum, running_mean, running_var, tracked);
+    DIR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fds_finalize_groups_tracked_kernel, dim3(dir_cdiv(nb, DIR_TPB)), dim3(DIR_TPB), 0, dir_s(stream),
+                       count, bin_ptr, nb, tracked);
+    DIR_LAUNCH_CHECK();
+    return DIR_OK;
+}
+
+extern "C" int dir_fds_finalize_update(const double* count, const double* mean, const double* m2, int nb, int C,
+                                       int factor_mode, double momentum,
+                                       float* running_mean, float* running_var, float* num_samples_tracked,
+                                       dir_stream_t stream) {
+    DIR_RETURN_IF(!count || !mean || !m2 || !running_mean || !running_var || !num_samples_tracked, DIR_EINVAL);
+    DIR_RETURN_IF(nb <= 0 || C <= 0 || factor_mode < 0 || factor_mode > 2, DIR_EINVAL);
+    return fds_finalize_launch(count, mean, m2, C, nullptr, nb, factor_mode, momentum, running_mean, running_var, num_samples_tracked, stream);
 }
 
 extern "C" int dir_fds_finalize_update_groups(const double* count, const double* mean, const double* m2, int ngroups, int C,
@@ -538,14 +539,7 @@ extern "C" int dir_fds_finalize_update_groups(const double* count, const double*
                                               float* running_mean, float* running_var, float* num_samples_tracked, dir_stream_t stream) {
     DIR_RETURN_IF(!count || !mean || !m2 || !bin_ptr || !running_mean || !running_var || !num_samples_tracked, DIR_EINVAL);
     DIR_RETURN_IF(ngroups <= 0 || nb <= 0 || C <= 0 || factor_mode < 0 || factor_mode > 2, DIR_EINVAL);
-    int gy = dir_cdiv(C, DIR_TPB); if (gy > 64) gy = 64;
-    hipLaunchKernelGGL(fds_finalize_groups_tables_kernel, dim3(nb, gy), dim3(DIR_TPB), 0, dir_s(stream),
-                       count, mean, m2, C, bin_ptr, factor_mode, momentum, running_mean, running_var, num_samples_tracked);
-    DIR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fds_finalize_groups_tracked_kernel, dim3(dir_cdiv(nb, DIR_TPB)), dim3(DIR_TPB), 0, dir_s(stream),
-                       count, bin_ptr, nb, num_samples_tracked);
-    DIR_LAUNCH_CHECK();
-    return DIR_OK;
+    return fds_finalize_launch(count, mean, m2, C, bin_ptr, nb, factor_mode, momentum, running_mean, running_var, num_samples_tracked, stream);
 }
 
 // =============================================================================================
@@ -590,28 +584,36 @@ extern "C" int dir_fds_smooth_bins(const float* mean, const float* var, const fl
 // =============================================================================================
 // K5a: multiplier table
 // =============================================================================================
+// One kernel for the three variants (utils.py:97-107; sts-b-dir/util.py:63-73, nyud2-dir/util.py:151-162); -1 = column left untouched.
+//   guard_mode 0: age variant — a column is left untouched when v1 == 0 (dir_fds_prepare_scale).
+//   guard_mode 1: the reference AS IT EXECUTES on torch >= 1.2 — `((v1 > 0.) + (v2 >= 0.)) == 2` adds two bool
+//                 tensors (logical or) and compares with 2, which is never true, so as soon as ANY column of the row
+//                 has v1 <= 0 or v2 < 0 the WHOLE row is returned unchanged.
+//   guard_mode 2: the evident intent (and the behaviour on the torch 0.4.1 the STS-B project pins): only the columns
+//                 with v1 <= 0 or v2 < 0 are left untouched.
 __global__ void __launch_bounds__(DIR_TPB)
-fds_prepare_scale_kernel(const float* __restrict__ v1, const float* __restrict__ v2, int C,
-                         float clip_min, float clip_max, float* __restrict__ scale) {
+fds_prepare_scale_ex_kernel(const float* __restrict__ v1, const float* __restrict__ v2, int C, float clip_min,
+                            float clip_max, int guard_mode, float* __restrict__ scale) {
     __shared__ double wsum[DIR_TPB / DIR_WAVE];
     const int b = blockIdx.x;
     const float* r1 = v1 + (size_t)b * C;
     const float* r2 = v2 + (size_t)b * C;
     double s = 0.0;
-    for (int c = threadIdx.x; c < C; c += DIR_TPB) s += (double)r1[c];
-    s = dir_wave_sum(s);
-    if ((threadIdx.x & (DIR_WAVE - 1)) == 0) wsum[threadIdx.x / DIR_WAVE] = s;
-    __syncthreads();
-    double tot = 0.0;
-#pragma unroll
-    for (int i = 0; i < DIR_TPB / DIR_WAVE; ++i) tot += wsum[i];
-    const bool row_identity = tot < 1e-10;                  // utils.py:98-99
+    int guard = 0;
     for (int c = threadIdx.x; c < C; c += DIR_TPB) {
-        const float a = r1[c];
-        float out;
-        if (row_identity || a == 0.0f) out = -1.0f;          // utils.py:100-104
-        else {
-            float q = r2[c] / a;
+        const float a = r1[c], bb = r2[c];
+        s += (double)a;
+        guard |= (a <= 0.0f) || (bb < 0.0f);                 // exactly the reference's `.any()` tests (NaN compares false)
+    }
+    const double tot = dir_block_sum(s, wsum);
+    const int any_guard = __syncthreads_or(guard);
+    const bool row_identity = (tot < 1e-10) || (guard_mode == 1 && any_guard);   // utils.py:98-99
+    for (int c = threadIdx.x; c < C; c += DIR_TPB) {
+        const float a = r1[c], bb = r2[c];
+        const bool untouched = row_identity || (guard_mode == 0 ? (a == 0.0f) : ((a <= 0.0f) || (bb < 0.0f)));
+        float out = -1.0f;
+        if (!untouched) {
+            float q = bb / a;
             q = (q < clip_min) ? clip_min : ((q > clip_max) ? clip_max : q);   // NaN falls through
             out = sqrtf(q);
         }
@@ -619,21 +621,36 @@ fds_prepare_scale_kernel(const float* __restrict__ v1, const float* __restrict__
     }
 }
 
-extern "C" int dir_fds_prepare_scale(const float* v1, const float* v2, int nb, int C, float clip_min, float clip_max,
-                                     float* scale, dir_stream_t stream) {
-    DIR_RETURN_IF(!v1 || !v2 || !scale || nb <= 0 || C <= 0, DIR_EINVAL);
-    hipLaunchKernelGGL(fds_prepare_scale_kernel, dim3(nb), dim3(DIR_TPB), 0, dir_s(stream),
-                       v1, v2, C, clip_min, clip_max, scale);
+extern "C" int dir_fds_prepare_scale_ex(const float* v1, const float* v2, int nb, int C, float clip_min, float clip_max,
+                                        int guard_mode, float* scale, dir_stream_t stream) {
+    DIR_RETURN_IF(!v1 || !v2 || !scale || nb <= 0 || C <= 0 || guard_mode < 0 || guard_mode > 2, DIR_EINVAL);
+    hipLaunchKernelGGL(fds_prepare_scale_ex_kernel, dim3(nb), dim3(DIR_TPB), 0, dir_s(stream), v1, v2, C, clip_min, clip_max,
+                       guard_mode, scale);
     DIR_LAUNCH_CHECK();
     return DIR_OK;
+}
+
+extern "C" int dir_fds_prepare_scale(const float* v1, const float* v2, int nb, int C, float clip_min, float clip_max,
+                                     float* scale, dir_stream_t stream) {
+    return dir_fds_prepare_scale_ex(v1, v2, nb, C, clip_min, clip_max, 0, scale, stream);
 }
 
 // =============================================================================================
 // K5 / K6: calibration forward (in place) and backward; fused label->bin variant for a batch
 // =============================================================================================
-__device__ __forceinline__ float calib1(float x, float m1, float s, float m2) {
+// The two element ops of every calibration kernel below, scalar and per float4 component: s < 0 marks an untouched column.
+__device__ __forceinline__ float fds_calib_fwd(float x, float m1, float s, float m2) {
     return (s < 0.0f) ? x : (x - m1) * s + m2;               // utils.py:107, contraction off
 }
+__device__ __forceinline__ float fds_calib_bwd(float g, float s) { return (s < 0.0f) ? g : g * s; }
+__device__ __forceinline__ float4 fds_calib_fwd(const float4& v, const float4& m1, const float4& s, const float4& m2) {
+    return make_float4(fds_calib_fwd(v.x, m1.x, s.x, m2.x), fds_calib_fwd(v.y, m1.y, s.y, m2.y),
+                       fds_calib_fwd(v.z, m1.z, s.z, m2.z), fds_calib_fwd(v.w, m1.w, s.w, m2.w));
+}
+__device__ __forceinline__ float4 fds_calib_bwd(const float4& g, const float4& s) {
+    return make_float4(fds_calib_bwd(g.x, s.x), fds_calib_bwd(g.y, s.y), fds_calib_bwd(g.z, s.z), fds_calib_bwd(g.w, s.w));
+}
+__device__ __forceinline__ float4 fds_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }   // table rows: cached loads
 
 template <int VEC, bool FUSED>
 __global__ void __launch_bounds__(DIR_TPB)
@@ -663,18 +680,12 @@ fds_calibrate_fwd_kernel(float* __restrict__ x, const int32_t* __restrict__ bins
         const int col = (blockIdx.y * DIR_TPB + threadIdx.x) * 4;
         if (col >= C) return;
         // the row is streamed (non-temporal: read once, written once) so that the three [Nb, C] tables stay L2 resident
-        typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-        f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(x + xo + col));
-        const float4 a = *reinterpret_cast<const float4*>(m1 + to + col);
-        const float4 s = *reinterpret_cast<const float4*>(scale + to + col);
-        const float4 c = *reinterpret_cast<const float4*>(m2 + to + col);
-        v.x = calib1(v.x, a.x, s.x, c.x); v.y = calib1(v.y, a.y, s.y, c.y);
-        v.z = calib1(v.z, a.z, s.z, c.z); v.w = calib1(v.w, a.w, s.w, c.w);
-        __builtin_nontemporal_store(v, reinterpret_cast<f32x4_t*>(x + xo + col));
+        const float4 v = fds_ldnt(x + xo + col);
+        fds_stnt(x + xo + col, fds_calib_fwd(v, fds_ld4(m1 + to + col), fds_ld4(scale + to + col), fds_ld4(m2 + to + col)));
     } else {
         const int col = blockIdx.y * DIR_TPB + threadIdx.x;
         if (col >= C) return;
-        x[xo + col] = calib1(x[xo + col], m1[to + col], scale[to + col], m2[to + col]);
+        x[xo + col] = fds_calib_fwd(x[xo + col], m1[to + col], scale[to + col], m2[to + col]);
     }
 }
 
@@ -689,17 +700,13 @@ fds_calibrate_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx,
         const int col = (blockIdx.y * DIR_TPB + threadIdx.x) * 4;
         if (col >= C) return;
         float4 g = fds_ldnt(dy + xo + col);
-        if (bin >= 0) {
-            const float4 s = *reinterpret_cast<const float4*>(scale + to + col);
-            g.x = s.x < 0.0f ? g.x : g.x * s.x; g.y = s.y < 0.0f ? g.y : g.y * s.y;
-            g.z = s.z < 0.0f ? g.z : g.z * s.z; g.w = s.w < 0.0f ? g.w : g.w * s.w;
-        }
+        if (bin >= 0) g = fds_calib_bwd(g, fds_ld4(scale + to + col));
         fds_stnt(dx + xo + col, g);
     } else {
         const int col = blockIdx.y * DIR_TPB + threadIdx.x;
         if (col >= C) return;
         float g = dy[xo + col];
-        if (bin >= 0) { const float s = scale[to + col]; g = s < 0.0f ? g : g * s; }
+        if (bin >= 0) g = fds_calib_bwd(g, scale[to + col]);
         dx[xo + col] = g;
     }
 }
@@ -720,28 +727,25 @@ fds_calibrate_narrow_kernel(float* __restrict__ x, const float* __restrict__ dy,
         const size_t xo = (size_t)row * C + col;
         if (BWD) {
             float4 g = fds_ldnt(dy + xo);
-            if (bin >= 0) {
-                const float4 sc = *reinterpret_cast<const float4*>(scale + (size_t)bin * C + col);
-                g.x = sc.x < 0.0f ? g.x : g.x * sc.x; g.y = sc.y < 0.0f ? g.y : g.y * sc.y;
-                g.z = sc.z < 0.0f ? g.z : g.z * sc.z; g.w = sc.w < 0.0f ? g.w : g.w * sc.w;
-            }
+            if (bin >= 0) g = fds_calib_bwd(g, fds_ld4(scale + (size_t)bin * C + col));
             fds_stnt(x + xo, g);
         } else {
             if (bin < 0) continue;
             const size_t to = (size_t)bin * C + col;
-            float4 v = fds_ldnt(x + xo);
-            const float4 a = *reinterpret_cast<const float4*>(m1 + to);
-            const float4 sc = *reinterpret_cast<const float4*>(scale + to);
-            const float4 c = *reinterpret_cast<const float4*>(m2 + to);
-            v.x = calib1(v.x, a.x, sc.x, c.x); v.y = calib1(v.y, a.y, sc.y, c.y);
-            v.z = calib1(v.z, a.z, sc.z, c.z); v.w = calib1(v.w, a.w, sc.w, c.w);
-            fds_stnt(x + xo, v);
+            const float4 v = fds_ldnt(x + xo);
+            fds_stnt(x + xo, fds_calib_fwd(v, fds_ld4(m1 + to), fds_ld4(scale + to), fds_ld4(m2 + to)));
         }
     }
 }
 
-static bool vec4_ok(int C, const void* a, const void* b, const void* c, const void* d) {
-    return (C % 4 == 0) && dir_aligned16(a) && dir_aligned16(b) && dir_aligned16(c) && dir_aligned16(d);
+// the wide row forms of the forward kernel: one workgroup per (row, block of DIR_TPB * VEC columns)
+template <bool FUSED>
+static void fds_calibrate_fwd_rows(bool vec4, float* x, const int32_t* bins_in, const float* labels, int B, int C, float lo, float hi,
+                                   const float* m1, const float* scale, const float* m2, int32_t* bins_out, hipStream_t s) {
+    if (vec4) hipLaunchKernelGGL((fds_calibrate_fwd_kernel<4, FUSED>), dim3(B, dir_cdiv(C, DIR_TPB * 4)), dim3(DIR_TPB), 0, s,
+                                 x, bins_in, labels, B, C, lo, hi, m1, scale, m2, bins_out);
+    else hipLaunchKernelGGL((fds_calibrate_fwd_kernel<1, FUSED>), dim3(B, dir_cdiv(C, DIR_TPB)), dim3(DIR_TPB), 0, s,
+                            x, bins_in, labels, B, C, lo, hi, m1, scale, m2, bins_out);
 }
 
 extern "C" int dir_fds_calibrate_fwd(void* x_inout, int dtype, const int32_t* bins, int B, int C,
@@ -751,18 +755,12 @@ extern "C" int dir_fds_calibrate_fwd(void* x_inout, int dtype, const int32_t* bi
     DIR_RETURN_IF(!x_inout || !bins || !m1 || !scale || !m2, DIR_EINVAL);
     DIR_RETURN_IF(dtype != DIR_F32, DIR_EUNSUPPORTED);
     float* x = static_cast<float*>(x_inout);
-    if (vec4_ok(C, x, m1, scale, m2) && C / 4 <= 128 && DIR_TPB % (C / 4) == 0) {
-        const int tpr = C / 4, rpb = DIR_TPB / tpr;
-        int grid = dir_cdiv(B, rpb); if (grid > 16384) grid = 16384;
-        hipLaunchKernelGGL(fds_calibrate_narrow_kernel<false>, dim3(grid), dim3(DIR_TPB), 0, dir_s(stream), x, nullptr, bins,
-                           (long long)B, C, tpr, m1, scale, m2);
-    } else if (vec4_ok(C, x, m1, scale, m2)) {
-        hipLaunchKernelGGL((fds_calibrate_fwd_kernel<4, false>), dim3(B, dir_cdiv(C, DIR_TPB * 4)), dim3(DIR_TPB), 0,
-                           dir_s(stream), x, bins, nullptr, B, C, 0.f, 0.f, m1, scale, m2, nullptr);
-    } else {
-        hipLaunchKernelGGL((fds_calibrate_fwd_kernel<1, false>), dim3(B, dir_cdiv(C, DIR_TPB)), dim3(DIR_TPB), 0,
-                           dir_s(stream), x, bins, nullptr, B, C, 0.f, 0.f, m1, scale, m2, nullptr);
-    }
+    const FdsRowLayout lay = fds_row_layout(C, {x, m1, scale, m2});
+    if (lay.form == FDS_ROWS_NARROW)
+        hipLaunchKernelGGL(fds_calibrate_narrow_kernel<false>, dim3(lay.narrow_grid(B)), dim3(DIR_TPB), 0, dir_s(stream), x, nullptr, bins,
+                           (long long)B, C, lay.tpr, m1, scale, m2);
+    else
+        fds_calibrate_fwd_rows<false>(lay.vec4(), x, bins, nullptr, B, C, 0.f, 0.f, m1, scale, m2, nullptr, dir_s(stream));
     DIR_LAUNCH_CHECK();
     return DIR_OK;
 }
@@ -775,12 +773,11 @@ extern "C" int dir_fds_calibrate_bwd(const void* dy, void* dx, int dtype, const 
     DIR_RETURN_IF(dtype != DIR_F32, DIR_EUNSUPPORTED);
     const float* g = static_cast<const float*>(dy);
     float* o = static_cast<float*>(dx);
-    if (vec4_ok(C, g, o, scale, scale) && C / 4 <= 128 && DIR_TPB % (C / 4) == 0) {
-        const int tpr = C / 4, rpb = DIR_TPB / tpr;
-        int grid = dir_cdiv(B, rpb); if (grid > 16384) grid = 16384;
-        hipLaunchKernelGGL(fds_calibrate_narrow_kernel<true>, dim3(grid), dim3(DIR_TPB), 0, dir_s(stream), o, g, bins,
-                           (long long)B, C, tpr, nullptr, scale, nullptr);
-    } else if (vec4_ok(C, g, o, scale, scale)) {
+    const FdsRowLayout lay = fds_row_layout(C, {g, o, scale});
+    if (lay.form == FDS_ROWS_NARROW) {
+        hipLaunchKernelGGL(fds_calibrate_narrow_kernel<true>, dim3(lay.narrow_grid(B)), dim3(DIR_TPB), 0, dir_s(stream), o, g, bins,
+                           (long long)B, C, lay.tpr, nullptr, scale, nullptr);
+    } else if (lay.form == FDS_ROWS_VEC4) {
         hipLaunchKernelGGL(fds_calibrate_bwd_kernel<4>, dim3(B, dir_cdiv(C, DIR_TPB * 4)), dim3(DIR_TPB), 0,
                            dir_s(stream), g, o, bins, C, scale);
     } else {
@@ -798,7 +795,7 @@ extern "C" int dir_fds_calibrate_bwd(const void* dy, void* dx, int dtype, const 
 // (3 x nb x 128 floats = 150 KB at nb = 100: one workgroup per CU, 1024 threads), then streams its range of feature rows in
 // their natural order: 32 lanes cover the 512-byte slice of a row, every lane keeps four rows in flight (non-temporal 16-byte
 // loads / stores), and the table values come from LDS with the row's bin as the index — conflict free (16 lanes of a
-// ds_read_b128 group read 256 contiguous bytes). No sort, no atomics, the arithmetic of calib1 unchanged: bit-identical results.
+// ds_read_b128 group read 256 contiguous bytes). No sort, no atomics, the arithmetic of fds_calib_fwd unchanged: bit-identical results.
 // Replaces imdb-wiki-dir/fds.py:120-143 / utils.py:97-107 for B >= FDS_LDS_MIN_ROWS and the NHWC form of the NYUD2 map.
 // ---------------------------------------------------------------------------------------------
 #define FDS_LDS_TPB 1024
@@ -849,11 +846,7 @@ fds_calibrate_lds_kernel(float* __restrict__ x, const int32_t* __restrict__ bins
         for (int u = 0; u < 4; ++u) {
             if (bn[u] < 0) continue;
             const long long r = row + (long long)u * RPP;
-            const float4 a = t1[bn[u] * TPR], sc = ts[bn[u] * TPR], c = t2[bn[u] * TPR];
-            float4 o;
-            o.x = calib1(v[u].x, a.x, sc.x, c.x); o.y = calib1(v[u].y, a.y, sc.y, c.y);
-            o.z = calib1(v[u].z, a.z, sc.z, c.z); o.w = calib1(v[u].w, a.w, sc.w, c.w);
-            fds_stnt(x + (size_t)r * C + col, o);
+            fds_stnt(x + (size_t)r * C + col, fds_calib_fwd(v[u], t1[bn[u] * TPR], ts[bn[u] * TPR], t2[bn[u] * TPR]));
         }
     }
 }
@@ -891,7 +884,7 @@ extern "C" int dir_fds_calibrate_fwd_lds(void* x_inout, int dtype, const int32_t
     DIR_RETURN_IF(!x_inout || !bins || !m1 || !scale || !m2, DIR_EINVAL);
     DIR_RETURN_IF(dtype != DIR_F32, DIR_EUNSUPPORTED);
     float* x = static_cast<float*>(x_inout);
-    if (vec4_ok(C, x, m1, scale, m2) && fds_calibrate_lds_launch(x, bins, B, C, nb, m1, scale, m2, dir_s(stream)) == 0) {
+    if (fds_row_layout(C, {x, m1, scale, m2}).vec4() && fds_calibrate_lds_launch(x, bins, B, C, nb, m1, scale, m2, dir_s(stream)) == 0) {
         DIR_LAUNCH_CHECK();
         return DIR_OK;
     }
@@ -946,8 +939,8 @@ fds_calibrate_nchw_kernel(const float* __restrict__ x, float* __restrict__ y, co
             for (int k = 0; k < 4; ++k) {
                 if (bn[k] < 0) { out[k] = in[k]; continue; }
                 const float sc = ts[c * nbp + bn[k]];
-                if (BWD) out[k] = sc < 0.0f ? in[k] : in[k] * sc;
-                else out[k] = calib1(in[k], t1[c * nbp + bn[k]], sc, t2[c * nbp + bn[k]]);
+                if (BWD) out[k] = fds_calib_bwd(in[k], sc);
+                else out[k] = fds_calib_fwd(in[k], t1[c * nbp + bn[k]], sc, t2[c * nbp + bn[k]]);
             }
             fds_stnt(y + base + (size_t)c * HW, make_float4(out[0], out[1], out[2], out[3]));
         }
@@ -958,7 +951,7 @@ fds_calibrate_nchw_kernel(const float* __restrict__ x, float* __restrict__ y, co
 // ONE channel plane (four 4 KB pieces in flight per workgroup) — the access pattern a bare stream prefers on this part (6.3 TB/s
 // against 4.2-5.1 for grid-stride sweeps, profiles/r03_stream_patterns.txt). A plane needs only its channel's COLUMN of the tables:
 // 3 x nb floats in LDS (1.1 KB, fetched from the L2-resident [nb][C] tables), the bins of the chunk's pixels come from the L2 too
-// (re-read once per channel: 2.2 MB x 128 at NYUD2 shapes). Same calib1 arithmetic: bit-identical to the kernel above.
+// (re-read once per channel: 2.2 MB x 128 at NYUD2 shapes). Same fds_calib_fwd / fds_calib_bwd arithmetic: bit-identical to the kernel above.
 template <bool BWD>
 __global__ void __launch_bounds__(DIR_TPB)
 fds_calibrate_nchw_plane_kernel(const float* __restrict__ x, float* __restrict__ y, const int32_t* __restrict__ bins,
@@ -997,8 +990,8 @@ fds_calibrate_nchw_plane_kernel(const float* __restrict__ x, float* __restrict__
         for (int k = 0; k < 4; ++k) {
             if (bn[k] < 0) { out[k] = in[k]; continue; }
             const float sc = tab[1][bn[k]];
-            if (BWD) out[k] = sc < 0.0f ? in[k] : in[k] * sc;
-            else out[k] = calib1(in[k], tab[0][bn[k]], sc, tab[2][bn[k]]);
+            if (BWD) out[k] = fds_calib_bwd(in[k], sc);
+            else out[k] = fds_calib_fwd(in[k], tab[0][bn[k]], sc, tab[2][bn[k]]);
         }
         fds_stnt(yp + p, make_float4(out[0], out[1], out[2], out[3]));
     }
@@ -1013,11 +1006,12 @@ static int fds_nchw_launch(bool bwd, const float* x, float* y, const int32_t* bi
     if (N == 0) return DIR_OK;
     DIR_RETURN_IF(!x || !y || !bins || !scale || (!bwd && (!m1 || !m2)), DIR_EINVAL);
     DIR_RETURN_IF((HW & 3) || !dir_aligned16(x) || !dir_aligned16(y) || !dir_aligned16(bins), DIR_EUNSUPPORTED);
+#define FDS_NCHW_GO(KERNEL_, ...)                                                   /* one argument list for the <BWD> pair */ \
+    { if (bwd) hipLaunchKernelGGL(KERNEL_<true>, __VA_ARGS__); else hipLaunchKernelGGL(KERNEL_<false>, __VA_ARGS__); }
     if (nb <= 128 && N * (long long)C * dir_cdiv(HW, 4096) < (1ll << 31)) {
         const int chunks = dir_cdiv(HW, 4096);
         const unsigned grid = (unsigned)(N * C * chunks);
-        if (bwd) hipLaunchKernelGGL(fds_calibrate_nchw_plane_kernel<true>, dim3(grid), dim3(DIR_TPB), 0, dir_s(stream), x, y, bins, C, HW, nb, chunks, m1, scale, m2);
-        else hipLaunchKernelGGL(fds_calibrate_nchw_plane_kernel<false>, dim3(grid), dim3(DIR_TPB), 0, dir_s(stream), x, y, bins, C, HW, nb, chunks, m1, scale, m2);
+        FDS_NCHW_GO(fds_calibrate_nchw_plane_kernel, dim3(grid), dim3(DIR_TPB), 0, dir_s(stream), x, y, bins, C, HW, nb, chunks, m1, scale, m2);
         DIR_LAUNCH_CHECK();
         return DIR_OK;
     }
@@ -1038,8 +1032,8 @@ static int fds_nchw_launch(bool bwd, const float* x, float* y, const int32_t* bi
     int grid = (int)(want < cap ? (want < 1 ? 1 : want) : cap);
     DIR_ONCE_PER_DEVICE((void)hipFuncSetAttribute(reinterpret_cast<const void*>(fds_calibrate_nchw_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fds_calibrate_nchw_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    if (bwd) hipLaunchKernelGGL(fds_calibrate_nchw_kernel<true>, dim3(grid, groups), dim3(FDS_LDS_TPB), lds, dir_s(stream), x, y, bins, npix, C, HW, nb, nbp, CG, m1, scale, m2);
-    else hipLaunchKernelGGL(fds_calibrate_nchw_kernel<false>, dim3(grid, groups), dim3(FDS_LDS_TPB), lds, dir_s(stream), x, y, bins, npix, C, HW, nb, nbp, CG, m1, scale, m2);
+    FDS_NCHW_GO(fds_calibrate_nchw_kernel, dim3(grid, groups), dim3(FDS_LDS_TPB), lds, dir_s(stream), x, y, bins, npix, C, HW, nb, nbp, CG, m1, scale, m2);
+#undef FDS_NCHW_GO
     DIR_LAUNCH_CHECK();
     return DIR_OK;
 }
@@ -1079,13 +1073,8 @@ extern "C" int dir_fds_smooth_fwd(void* x_inout, int dtype, const float* labels,
             return dir_fds_calibrate_fwd_lds(x_inout, dtype, bins_out, B, C, bucket_num - bucket_start, m1, scale, m2, stream);
         return dir_fds_calibrate_fwd(x_inout, dtype, bins_out, B, C, m1, scale, m2, stream);
     }
-    if (vec4_ok(C, x, m1, scale, m2)) {
-        hipLaunchKernelGGL((fds_calibrate_fwd_kernel<4, true>), dim3(B, dir_cdiv(C, DIR_TPB * 4)), dim3(DIR_TPB), 0,
-                           dir_s(stream), x, nullptr, labels, B, C, lo, hi, m1, scale, m2, bins_out);
-    } else {
-        hipLaunchKernelGGL((fds_calibrate_fwd_kernel<1, true>), dim3(B, dir_cdiv(C, DIR_TPB)), dim3(DIR_TPB), 0,
-                           dir_s(stream), x, nullptr, labels, B, C, lo, hi, m1, scale, m2, bins_out);
-    }
+    fds_calibrate_fwd_rows<true>(fds_row_layout(C, {x, m1, scale, m2}).vec4(), x, nullptr, labels, B, C, lo, hi, m1, scale, m2, bins_out,
+                                 dir_s(stream));
     DIR_LAUNCH_CHECK();
     return DIR_OK;
 }
@@ -1152,57 +1141,6 @@ extern "C" int dir_fds_fill_empty_buckets(const double* count, int nb, int C, fl
     DIR_LAUNCH_CHECK();
     return DIR_OK;
 }
-
-// Multiplier table with the STS-B / NYUD2 guards (sts-b-dir/util.py:63-73, nyud2-dir/util.py:151-162).
-//   guard_mode 0: age variant — a column is left untouched when v1 == 0.
-//   guard_mode 1: the reference AS IT EXECUTES on torch >= 1.2 — `((v1 > 0.) + (v2 >= 0.)) == 2` adds two bool
-//                 tensors (logical or) and compares with 2, which is never true, so as soon as ANY column of the row
-//                 has v1 <= 0 or v2 < 0 the WHOLE row is returned unchanged.
-//   guard_mode 2: the evident intent (and the behaviour on the torch 0.4.1 the STS-B project pins): only the columns
-//                 with v1 <= 0 or v2 < 0 are left untouched.
-__global__ void __launch_bounds__(DIR_TPB)
-fds_prepare_scale_ex_kernel(const float* __restrict__ v1, const float* __restrict__ v2, int C, float clip_min,
-                            float clip_max, int guard_mode, float* __restrict__ scale) {
-    __shared__ double wsum[DIR_TPB / DIR_WAVE];
-    const int b = blockIdx.x;
-    const float* r1 = v1 + (size_t)b * C;
-    const float* r2 = v2 + (size_t)b * C;
-    double s = 0.0;
-    int guard = 0;
-    for (int c = threadIdx.x; c < C; c += DIR_TPB) {
-        const float a = r1[c], bb = r2[c];
-        s += (double)a;
-        guard |= (a <= 0.0f) || (bb < 0.0f);                 // exactly the reference's `.any()` tests (NaN compares false)
-    }
-    s = dir_wave_sum(s);
-    if ((threadIdx.x & (DIR_WAVE - 1)) == 0) wsum[threadIdx.x / DIR_WAVE] = s;
-    const int any_guard = __syncthreads_or(guard);
-    double tot = 0.0;
-#pragma unroll
-    for (int i = 0; i < DIR_TPB / DIR_WAVE; ++i) tot += wsum[i];
-    const bool row_identity = (tot < 1e-10) || (guard_mode == 1 && any_guard);
-    for (int c = threadIdx.x; c < C; c += DIR_TPB) {
-        const float a = r1[c], bb = r2[c];
-        const bool untouched = row_identity || (guard_mode == 0 ? (a == 0.0f) : ((a <= 0.0f) || (bb < 0.0f)));
-        float out = -1.0f;
-        if (!untouched) {
-            float q = bb / a;
-            q = (q < clip_min) ? clip_min : ((q > clip_max) ? clip_max : q);
-            out = sqrtf(q);
-        }
-        scale[(size_t)b * C + c] = out;
-    }
-}
-
-extern "C" int dir_fds_prepare_scale_ex(const float* v1, const float* v2, int nb, int C, float clip_min, float clip_max,
-                                        int guard_mode, float* scale, dir_stream_t stream) {
-    DIR_RETURN_IF(!v1 || !v2 || !scale || nb <= 0 || C <= 0 || guard_mode < 0 || guard_mode > 2, DIR_EINVAL);
-    hipLaunchKernelGGL(fds_prepare_scale_ex_kernel, dim3(nb), dim3(DIR_TPB), 0, dir_s(stream), v1, v2, C, clip_min, clip_max,
-                       guard_mode, scale);
-    DIR_LAUNCH_CHECK();
-    return DIR_OK;
-}
-
 
 // =============================================================================================
 // NYUD2-DIR dense variant (nyud2-dir/models/fds.py:51-53, :138-139): bucket = clamp(int(label * 10), start, num - 1)

@@ -43,18 +43,6 @@ __device__ __forceinline__ void loss_elem(const LossArgs a, float x, float y, fl
     val = v; grad = g;
 }
 
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-    v = dir_wave_sum(v);
-    const int wid = threadIdx.x / DIR_WAVE;
-    if ((threadIdx.x & (DIR_WAVE - 1)) == 0) sh[wid] = v;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int i = 0; i < DIR_TPB / DIR_WAVE; ++i) t += sh[i];
-    __syncthreads();
-    return t;
-}
-
 // One workgroup: whole loss in one launch (the training-batch case, n = B).
 __global__ void __launch_bounds__(DIR_TPB)
 loss_single_kernel(LossArgs a, const float* __restrict__ x, const float* __restrict__ y,
@@ -68,7 +56,7 @@ loss_single_kernel(LossArgs a, const float* __restrict__ x, const float* __restr
         acc += (double)v;
         if (dx) dx[i] = g * inv_n;
     }
-    const double tot = block_sum(acc, sh);
+    const double tot = dir_block_sum(acc, sh);
     if (threadIdx.x == 0) loss[0] = (float)(tot / (double)n);
 }
 
@@ -85,7 +73,7 @@ loss_partial_kernel(LossArgs a, const float* __restrict__ x, const float* __rest
         acc += (double)v;
         if (dx) dx[i] = g * inv_n;
     }
-    const double tot = block_sum(acc, sh);
+    const double tot = dir_block_sum(acc, sh);
     if (threadIdx.x == 0) partial[blockIdx.x] = tot;
 }
 
@@ -94,7 +82,7 @@ loss_final_kernel(const double* __restrict__ partial, int nparts, int n, float* 
     __shared__ double sh[DIR_TPB / DIR_WAVE];
     double acc = 0.0;
     for (int i = threadIdx.x; i < nparts; i += DIR_TPB) acc += partial[i];
-    const double tot = block_sum(acc, sh);
+    const double tot = dir_block_sum(acc, sh);
     if (threadIdx.x == 0) loss[0] = (float)(tot / (double)n);
 }
 

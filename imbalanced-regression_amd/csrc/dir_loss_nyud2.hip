@@ -80,15 +80,8 @@ depth_loss_kernel(const float* __restrict__ pred, const float* __restrict__ dept
             }
         }
     }
-    acc = dir_wave_sum(acc);
-    if ((threadIdx.x & (DIR_WAVE - 1)) == 0) sh[threadIdx.x / DIR_WAVE] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double tot = 0.0;
-#pragma unroll
-        for (int wv = 0; wv < DIR_TPB / DIR_WAVE; ++wv) tot += sh[wv];            // wave order
-        partials[blockIdx.x] = tot;
-    }
+    const double tot = dir_block_sum(acc, sh);                                    // wave order
+    if (threadIdx.x == 0) partials[blockIdx.x] = tot;
 }
 
 static_assert(DLOSS_MAX_BLOCKS <= DIR_TPB, "the fold stages one partial per thread");

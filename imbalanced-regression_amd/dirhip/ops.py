@@ -132,12 +132,8 @@ def prepare_scale(v1, v2, clip_min=0.1, clip_max=10.0, out=None, guard_mode=0):
     v2 = L.require_device_tensor(v2, f32, "v2")
     nb, c = v1.shape
     scale = torch.empty_like(v1) if out is None else out
-    if guard_mode == 0:
-        L.check(L.lib().dir_fds_prepare_scale(L.ptr(v1), L.ptr(v2), nb, c, clip_min, clip_max, L.ptr(scale),
-                                              L.stream_ptr(v1.device)), "dir_fds_prepare_scale")
-    else:
-        L.check(L.lib().dir_fds_prepare_scale_ex(L.ptr(v1), L.ptr(v2), nb, c, clip_min, clip_max, guard_mode, L.ptr(scale),
-                                                 L.stream_ptr(v1.device)), "dir_fds_prepare_scale_ex")
+    L.check(L.lib().dir_fds_prepare_scale_ex(L.ptr(v1), L.ptr(v2), nb, c, clip_min, clip_max, guard_mode, L.ptr(scale),
+                                             L.stream_ptr(v1.device)), "dir_fds_prepare_scale_ex")
     return scale
 
 
