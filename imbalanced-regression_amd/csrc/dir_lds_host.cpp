@@ -111,6 +111,43 @@ extern "C" int dir_lds_weights(const double* labels, int64_t n, int max_target, 
     return DIR_OK;
 }
 
+// sts-b-dir/tasks.py:44-73: the same arithmetic over histogram buckets (np.histogram edges, float32 comparisons) instead of int(label).
+extern "C" int dir_lds_weights_binned(const float* labels, int64_t n, const float* edges, int num_bins, int reweight, int lds,
+                                      const double* window, int ks, float* weights) {
+    if (!labels || !edges || !weights || n <= 0 || num_bins <= 0) return DIR_EINVAL;
+    if (reweight != DIR_REWEIGHT_SQRT_INV && reweight != DIR_REWEIGHT_INVERSE) return DIR_EINVAL;
+    if (lds && (!window || ks <= 0 || (ks & 1) == 0)) return DIR_EINVAL;
+    std::vector<int32_t> bin(n);
+    std::vector<int64_t> counts(num_bins, 0);                                                    // :49 np.histogram
+    for (int64_t i = 0; i < n; ++i) {
+        const float l = labels[i];
+        if (!(l >= edges[0] && l <= edges[num_bins])) return DIR_EINVAL;                         // outside the range / NaN
+        int lo = 0, hi = num_bins + 1;                                                           // :51-55 first edge > label, minus one
+        while (lo < hi) {
+            const int mid = (lo + hi) / 2;
+            if (edges[mid] <= l) lo = mid + 1; else hi = mid;
+        }
+        const int b = lo - 1 > num_bins - 1 ? num_bins - 1 : lo - 1;                             // label == last edge: the last bin
+        bin[i] = b;
+        counts[b] += 1;
+    }
+    std::vector<double> value(num_bins);
+    const bool integer_valued = (reweight == DIR_REWEIGHT_INVERSE);
+    for (int k = 0; k < num_bins; ++k)
+        value[k] = integer_valued ? (double)counts[k] : std::sqrt((double)counts[k]);             // :57-58, no clip
+    if (lds) {                                                                                   // :63-67
+        std::vector<double> sm(num_bins);
+        convolve1d_constant(value.data(), num_bins, window, ks, sm.data());
+        for (int k = 0; k < num_bins; ++k)
+            value[k] = integer_valued ? (double)(int64_t)sm[k] : sm[k];    // int64 input array -> int64 output: C truncation (A.5)
+    }
+    for (int64_t i = 0; i < n; ++i) weights[i] = (float)(1.0 / value[bin[i]]);                   // :69 np.float32(1 / x)
+    const float total = numpy_sum_f32(weights, n);                                               // :70 float32 np.sum
+    const float scaling = (float)n / total;                                                      //     int / float32 -> float32
+    for (int64_t i = 0; i < n; ++i) weights[i] = scaling * weights[i];                           // :71
+    return DIR_OK;
+}
+
 extern "C" int dir_abi_version(void) { return DIR_ABI_VERSION; }
 
 extern "C" const char* dir_error_string(int code) {

@@ -145,6 +145,9 @@ SIGNATURES = {
     "dir_age_eval_accumulate": (c_int, [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dir_depth_loss_workspace": (c_size_t, [c_longlong]),
     "dir_depth_loss": (c_int, [c_void_p, c_void_p, c_longlong, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dir_stsb_eval_workspace": (c_size_t, [c_longlong, c_int]),
+    "dir_stsb_eval": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dir_lds_weights_binned": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
 }
 
 ABI_VERSION = 4

@@ -325,6 +325,37 @@ def age_eval_accumulate(pred, label, valid, table):
     return table
 
 
+# ---- STS-B evaluation (sts-b-dir/util.py STSShotAverage) --------------------------------------------------------------------------
+def stsb_eval(pred, label, edges, group_of_bin):
+    """pred / label f32 of equal element count (the whole evaluation set, at most 65536), edges [num_bins + 1] f32, group_of_bin
+    [num_bins] uint8 (0 many / 1 medium / 2 few), all on one device -> (moments [4, 10] f64, ranks [4, 5] int64), two views of ONE
+    60-word device buffer (``.base`` is that buffer: one copy reads both). Three launches; enqueue only, no sync. ``ranks[3, 0] < 0``
+    reports invalid samples (include/dir_hip.h); the caller checks it after the read-back."""
+    pred = L.require_device_tensor(pred, f32, "pred").view(-1)
+    label = L.require_device_tensor(label, f32, "label").view(-1)
+    edges = L.require_device_tensor(edges, f32, "edges")
+    group_of_bin = L.require_device_tensor(group_of_bin, torch.uint8, "group_of_bin")
+    if pred.numel() != label.numel():
+        raise ValueError(f"pred and label differ in size: {pred.numel()} vs {label.numel()}")
+    num_bins = group_of_bin.numel()
+    if edges.dim() != 1 or edges.numel() != num_bins + 1:
+        raise ValueError("edges must be [num_bins + 1] for group_of_bin [num_bins]")
+    dev = label.device
+    if pred.device != dev or edges.device != dev or group_of_bin.device != dev:
+        raise ValueError("pred, label, edges and group_of_bin must live on one device")
+    n = label.numel()
+    nbytes = L.lib().dir_stsb_eval_workspace(n, num_bins)
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _EVAL_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _EVAL_WS[key] = _ws(nbytes, dev)
+    both = torch.empty(60, dtype=torch.int64, device=dev)
+    moments, ranks = both[:40].view(f64).view(4, 10), both[40:].view(4, 5)
+    L.check(L.lib().dir_stsb_eval(L.ptr(pred), L.ptr(label), n, L.ptr(edges), num_bins, L.ptr(group_of_bin), L.ptr(moments), L.ptr(ranks),
+                                  L.ptr(ws), ws.numel(), L.stream_ptr(dev)), "dir_stsb_eval")
+    return moments, ranks
+
+
 # ---- K8 (host) ------------------------------------------------------------------------------------
 def lds_weights(labels, max_target, reweight, lds, window):
     """labels: any 1-D array-like (host). Returns np.float32 [n]."""
@@ -336,4 +367,19 @@ def lds_weights(labels, max_target, reweight, lds, window):
                                  1 if lds else 0, None if win is None else win.ctypes.data_as(ctypes.c_void_p),
                                  0 if win is None else win.shape[0], out.ctypes.data_as(ctypes.c_void_p))
     L.check(rc, "dir_lds_weights")
+    return out
+
+
+def lds_weights_binned(labels, edges, reweight, lds, window):
+    """labels: 1-D float32 array-like (host), edges [num_bins + 1] float32. Returns np.float32 [n] (sts-b-dir/tasks.py:44-73)."""
+    lab = np.ascontiguousarray(np.asarray(labels, dtype=np.float32).reshape(-1))
+    edg = np.ascontiguousarray(np.asarray(edges, dtype=np.float32).reshape(-1))
+    n = lab.shape[0]
+    out = np.empty(n, dtype=np.float32)
+    win = None if window is None else np.ascontiguousarray(np.asarray(window, dtype=np.float64))
+    rc = L.lib().dir_lds_weights_binned(lab.ctypes.data_as(ctypes.c_void_p), n, edg.ctypes.data_as(ctypes.c_void_p), edg.shape[0] - 1,
+                                        L.REWEIGHT[reweight], 1 if lds else 0,
+                                        None if win is None else win.ctypes.data_as(ctypes.c_void_p),
+                                        0 if win is None else win.shape[0], out.ctypes.data_as(ctypes.c_void_p))
+    L.check(rc, "dir_lds_weights_binned")
     return out

@@ -208,6 +208,19 @@ int dir_scale_by_device_scalar(const float* in, const float* scalar, float* out,
 int dir_lds_weights(const double* labels, int64_t n, int max_target, int reweight, int lds,
                     const double* window, int ks, float* weights);
 
+/* LDS per-sample weights for labels bucketed by histogram edges — HOST function.  Replaces sts-b-dir/tasks.py:44-73, bit for bit:
+ *   counts = np.histogram(labels, bins=num_bins, range=(edges[0], edges[num_bins])) (int64); bin of a label as tasks.py:51-55:
+ *   (number of edges <= label) - 1, label == edges[num_bins] -> num_bins - 1, comparisons in float32;
+ *   sqrt_inv: float64 sqrt of the counts; inverse: the int64 counts, NOT clipped to 5..1000 as the age projects do;
+ *   if lds: scipy.ndimage.convolve1d(mode='constant') with `window` [ks] f64; for `inverse` the output array is int64, so the
+ *           smoothed values are truncated to integers;
+ *   w_i = (f32)(1 / value[bin_i]) (an empty smoothed bucket gives inf, as the reference); scaling = (f32)n / numpy_f32_sum(w);
+ *   weights[i] = scaling * w_i in float32.
+ * edges [num_bins + 1] f32 ascending.  DIR_EINVAL: a label outside [edges[0], edges[num_bins]] or NaN (the reference raises
+ * IndexError above the range and wraps a negative index below it), NULL pointers, n <= 0, num_bins <= 0, an even ks. */
+int dir_lds_weights_binned(const float* labels, int64_t n, const float* edges, int num_bins, int reweight, int lds,
+                           const double* window, int ks, float* weights);
+
 /* ---------------------------------------------------------------------------------------------
  * K9a  BatchNorm2d (+ residual add) (+ ReLU), NHWC activations, training and eval forward, backward.
  * Replaces, for each of the 53 BN layers of imdb-wiki-dir/resnet.py (Bottleneck.forward :57-70, stem :128-130,
@@ -702,6 +715,39 @@ int dir_age_eval_accumulate(const float* pred, const float* label, const uint8_t
 size_t dir_depth_loss_workspace(long long n);
 int dir_depth_loss(const float* pred, const float* depth, long long n, float mult, const float* table, int bucket_num,
                    float* loss, float* dx_unit, void* workspace, size_t workspace_bytes, dir_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Balanced STS-B evaluation (sts-b-dir/util.py:101-172 `STSShotAverage.get_metric`): the sums behind MSE / L1 / G-Mean / Pearson /
+ * Spearman per shot group, over the WHOLE evaluation set (Spearman's rho needs ranks over the set; it does not add over batches).
+ *   pred, label [n] f32 (pred is the network output in [0, 1]; the reference scores 5 * pred, util.py:143), any 4-byte alignment.
+ *   edges [num_bins + 1] f32 ascending (the reference's np.histogram(..., bins, range=(0., 5.)) edges, util.py:115-116, passed in, not
+ *   recomputed); group_of_bin [num_bins] uint8 with values 0 many / 1 medium / 2 few (util.py:109-113, :130-136).
+ *   Bin of a label (util.py:117-120): (number of edges <= label) - 1 by a search over the edge table, label == edges[num_bins] goes
+ *   to the last bin; comparisons in float32.
+ *   moments [4][10] f64, rows many / medium / few / overall, columns
+ *     NUM, [d == 0], sum d^2, sum d, sum ln d (d > 0), sum p', sum l', sum p'^2, sum l'^2, sum p'l'
+ *   with p = 5.0 * (double)pred, l = (double)label, d = |p - l|, p' = p - 2.5, l' = l - 2.5, every operation one float64 rounding.
+ *   Sums in a fixed order (wavefront butterfly per group, wave order, one partial per workgroup, workgroup order; the overall row is
+ *   (many + medium) + few): bit-reproducible, no float atomics.
+ *   ranks [4][5] int64, same rows, columns sum a, sum b, sum a^2, sum b^2, sum ab, where for sample i of a group
+ *     a = 2 * #{j in the group: pred_j < pred_i} + #{j in the group: pred_j == pred_i} + 1
+ *   is twice its average rank with ties (scipy.stats.rankdata) and b the same for label; the overall row ranks over every sample.
+ *   The raw float32 pred is compared: 5.0 * (double)pred is exact and monotone, so the ranks of 5 * pred are those of pred.  O(n^2)
+ *   compares, no sort; integers throughout, so the table is exact and does not depend on the order of the samples.
+ *   Both tables are WRITTEN (not accumulated into).  Three launches, no host synchronisation.
+ *   Invalid samples: a label below edges[0], above edges[num_bins] or NaN, a NaN prediction, or a group_of_bin value above 2 (the
+ *   reference raises IndexError above 5 and silently counts a negative label as "few").  They are in no sum; their number is
+ *   reported in ONE slot: ranks[3][0] (the overall sum a, otherwise >= n > 0) is then MINUS that number and the rest of both tables
+ *   is meaningless.  The caller must test ranks[3][0] < 0 (dirhip.ops.stsb_eval's caller raises DirHipError).
+ *   n <= 65536: the counters are uint32 and the largest sum, sum ab <= n * (2n)^2 = 4n^3 = 2^50 at the cap, stays far inside 63
+ *   bits (4n^3 < 2^63 up to n = 2^20; the cap is where the O(n^2) pass stops being a sensible evaluator, not where integers end).
+ *   workspace >= dir_stsb_eval_workspace(n, num_bins) bytes, 8-byte aligned (0 for unsupported arguments).
+ *   DIR_EINVAL: n <= 0, num_bins <= 0, a NULL or misaligned pointer.  DIR_EUNSUPPORTED: n > 65536, num_bins > 256 (LDS edge table).
+ *   DIR_EWORKSPACE: workspace too small. */
+size_t dir_stsb_eval_workspace(long long n, int num_bins);
+int dir_stsb_eval(const float* pred, const float* label, long long n, const float* edges, int num_bins,
+                  const uint8_t* group_of_bin, double* moments, long long* ranks, void* workspace, size_t workspace_bytes,
+                  dir_stream_t stream);
 
 #ifdef __cplusplus
 }
