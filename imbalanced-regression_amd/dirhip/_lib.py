@@ -148,6 +148,11 @@ SIGNATURES = {
     "dir_stsb_eval_workspace": (c_size_t, [c_longlong, c_int]),
     "dir_stsb_eval": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dir_lds_weights_binned": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "dir_jpeg_inspect": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "dir_jpeg_entropy_decode": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
+    "dir_jpeg_reconstruct_workspace": (c_size_t, [c_longlong]),
+    "dir_jpeg_reconstruct": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, c_longlong, c_longlong, c_void_p, c_longlong,
+                                     c_void_p, c_size_t, c_void_p]),
 }
 
 ABI_VERSION = 4

@@ -2,8 +2,9 @@
 
 Same constructor and ``__getitem__ -> (img f32[3,S,S], label f32[1], weight f32[1])`` contract; ``.weights`` comes
 from the native LDS routine (``dirhip.lds.prepare_weights`` -> ``dir_lds_weights``, bit-exact with the reference's
-numpy/scipy arithmetic). Image decoding is host-side PIL (the reference uses torchvision transforms, which this image does not
-ship; no GPU JPEG decoder either); Resize is host-side PIL by default and, with ``raw="decoded"`` + ``DeviceResize``, three HIP launches
+numpy/scipy arithmetic). Image decoding is host-side PIL by default (the reference uses torchvision transforms, which this image does not
+ship) and, with ``raw="bytes"`` + ``dirhip.jpeg.DeviceJpeg``, entropy decode in host threads + reconstruction on the GPU (``dir_jpeg_reconstruct``);
+Resize is host-side PIL by default and, with ``raw="decoded"`` + ``DeviceResize``, three HIP launches
 on the ragged uint8 batch (``dir_resize_u8``: Pillow's bilinear arithmetic bit for bit); the rest of the transform chain — RandomCrop(pad 16) -> RandomHorizontalFlip ->
 [0,1] -> Normalize(.5, .5) (datasets.py:38-53) — runs either on the host (numpy, the default ``__getitem__`` contract) or,
 with ``raw=True`` + ``DeviceAugment``, as ONE HIP launch per batch on the uint8 images (``dir_augment_u8``):
@@ -77,6 +78,24 @@ def ragged_collate(samples):
     weights = torch.from_numpy(np.stack([np.asarray(s[2], dtype=np.float32) for s in samples]))
     extra = tuple(torch.as_tensor([s[i] for s in samples]) for i in range(3, len(samples[0])))      # e.g. the shard-padding flag
     return (flat, sizes, labels, weights) + extra
+
+
+def bytes_collate(samples):
+    """collate_fn for ``raw="bytes"`` datasets (nothing is decoded in the workers): a batch is
+    ``(blob uint8 [sum of file sizes], lengths int64 [B], labels float32 [B, 1], weights float32 [B, 1][, further per-sample items])`` — the
+    files back to back, so that a batch crosses the worker boundary as ONE shared-memory block instead of one per file.
+    ``split_files(blob, lengths)`` is the list ``dirhip.jpeg.DeviceJpeg.decode`` takes."""
+    blob = torch.cat([s[0].reshape(-1) for s in samples])
+    lengths = torch.tensor([s[0].numel() for s in samples], dtype=torch.int64)
+    labels = torch.from_numpy(np.stack([np.asarray(s[1], dtype=np.float32) for s in samples]))
+    weights = torch.from_numpy(np.stack([np.asarray(s[2], dtype=np.float32) for s in samples]))
+    extra = tuple(torch.as_tensor([s[i] for s in samples]) for i in range(3, len(samples[0])))
+    return (blob, lengths, labels, weights) + extra
+
+
+def split_files(blob, lengths):
+    """The per-file uint8 views of a ``bytes_collate`` batch (no copy)."""
+    return list(torch.split(blob, [int(n) for n in lengths]))
 
 
 class DeviceResize:
@@ -257,7 +276,9 @@ class _AgeDataset(data.Dataset):
                  lds=False, lds_kernel='gaussian', lds_ks=5, lds_sigma=2, raw=False):
         # raw=True (extension): __getitem__ returns the decoded, resized uint8 HWC image instead of the transformed float
         # tensor; the rest of the transform chain then runs on the GPU (DeviceAugment). raw="decoded": decoded only, at the file's
-        # own size — Resize runs on the GPU too (DeviceResize; batches through ragged_collate)
+        # own size — Resize runs on the GPU too (DeviceResize; batches through ragged_collate). raw="bytes": the file's bytes as a uint8
+        # tensor, neither opened nor decoded — JPEG decode runs in the training process (dirhip.jpeg.DeviceJpeg: entropy decode in host
+        # threads, reconstruction on the GPU; batches through bytes_collate)
         self.raw = raw
         self.df = df
         self.data_dir = data_dir
@@ -300,8 +321,11 @@ class _AgeDataset(data.Dataset):
         from PIL import Image
         index = index % len(self.df)
         row = self.df.iloc[index]
-        img = Image.open(os.path.join(self.data_dir, row['path'])).convert('RGB')
-        img = self.get_transform()(img)
+        if self.raw == "bytes":
+            img = torch.from_numpy(np.fromfile(os.path.join(self.data_dir, row['path']), dtype=np.uint8))
+        else:
+            img = Image.open(os.path.join(self.data_dir, row['path'])).convert('RGB')
+            img = self.get_transform()(img)
         label = np.asarray([row['age']]).astype('float32')
         weight = np.asarray([self.weights[index]]).astype('float32') if self.weights is not None else \
             np.asarray([np.float32(1.)])

@@ -97,6 +97,14 @@ def build_parser(dataset_default='imdb_wiki'):
                    'RandomCrop / flip / ToTensor / Normalize run as one HIP kernel per batch (dir_augment_u8) instead of per image on the host')
     p.add_argument('--gpu_resize', action='store_true', help='image files only, implies --gpu_augment: loader workers only DECODE; Resize((S, S)) runs on the '
                    'GPU as well (dir_resize_u8: Pillow\'s bilinear arithmetic bit for bit, on the ragged uint8 batch), then dir_augment_u8')
+    p.add_argument('--gpu_decode', action='store_true', help='image files only, implies --gpu_resize: loader workers only READ the files; JPEG decode runs in '
+                   'the training process — markers and Huffman entropy decode in --decode_threads host threads on the compressed bytes, dequantisation / '
+                   'inverse DCT / chroma upsampling / YCbCr->RGB on the GPU (dir_jpeg_reconstruct, bit for bit libjpeg as Pillow drives it), then '
+                   'dir_resize_u8 and dir_augment_u8. Decoded natively: baseline and extended-sequential Huffman JPEGs with one interleaved scan, '
+                   'grayscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0, up to 8192 x 8192. Decoded by Pillow on the host instead (same pixels, per file): progressive, '
+                   'arithmetic-coded, 12-bit, multi-scan, CMYK / YCCK / RGB-coded and any Adobe-marked JPEG, other sampling factors (4:4:0, 4:1:1), '
+                   'damaged scans, and every non-JPEG format (PNG ...)')
+    p.add_argument('--decode_threads', type=int, default=8, help='host threads of --gpu_decode (at most 16)')
     p.add_argument('--gpu_cache', action='store_true', help='image files only, with --gpu_augment / --gpu_resize: keep the resized uint8 training images in HBM '
                    '(datasets.DeviceImageCache: 28.8 GB for IMDB-WIKI at 224); the FDS feature pass of the same epoch and every later epoch gather them '
                    'there and draw a fresh augmentation on the GPU: no JPEG decode after the first training pass. NOTE (more than one rank): the partition '
@@ -139,16 +147,21 @@ class _NullTB:
         pass
 
 
-def _loader_batches(loader, device, augment=None, resize=None, cache=None):
+def _loader_batches(loader, device, augment=None, resize=None, cache=None, decode=None):
     """``augment``: a ``datasets.DeviceAugment`` when the dataset is in raw mode — the uint8 batch goes over PCIe (a quarter of the
     float32 bytes) and crop / flip / normalise / cast run as one kernel on the GPU. ``resize``: a ``datasets.DeviceResize``
     when the workers only decode (``raw="decoded"`` + ``ragged_collate``): the batch arrives as (flat bytes, sizes, ...). On a GPU the
     device half runs ahead of the loop in ``datasets.DevicePrefetcher`` (side stream + thread): the copies never wait for the training stream.
-    ``cache``: a ``datasets.DeviceImageCache``; the batch then carries its sample indices as the last item and its resized bytes are stored."""
+    ``cache``: a ``datasets.DeviceImageCache``; the batch then carries its sample indices as the last item and its resized bytes are stored.
+    ``decode``: a ``jpeg.DeviceJpeg`` when the workers only read the files (``raw="bytes"`` + ``bytes_collate``): the batch arrives as (file bytes,
+    lengths, ...) and becomes the (flat, sizes, ...) batch ``resize`` takes."""
     def to_device(batch):
         index = None
         if cache is not None:
             index, batch = batch[-1], tuple(batch[:-1])
+        if decode is not None:
+            from .datasets import split_files
+            batch = tuple(decode.decode(split_files(batch[0], batch[1]))) + tuple(batch[2:])
         if resize is not None:
             inputs = resize(batch[0], batch[1])
             batch = (inputs,) + tuple(batch[2:])
@@ -379,7 +392,8 @@ def run(argv=None, dataset_default='imdb_wiki'):
         df_train, df_val, df_test = df[df['split'] == 'train'], df[df['split'] == 'val'], df[df['split'] == 'test']
         train_labels = df_train['age']
         cls = datasets.IMDBWIKI if args.dataset == 'imdb_wiki' else datasets.AgeDB
-        raw = "decoded" if args.gpu_resize else bool(args.gpu_augment)
+        args.gpu_resize = args.gpu_resize or args.gpu_decode
+        raw = "bytes" if args.gpu_decode else ("decoded" if args.gpu_resize else bool(args.gpu_augment))
         train_set = cls(data_dir=args.data_dir, df=df_train, img_size=args.img_size, split='train', reweight=args.reweight,
                         lds=args.lds, lds_kernel=args.lds_kernel, lds_ks=args.lds_ks, lds_sigma=args.lds_sigma, raw=raw)
         val_set = cls(data_dir=args.data_dir, df=df_val, img_size=args.img_size, split='val', raw=raw)
@@ -389,7 +403,11 @@ def run(argv=None, dataset_default='imdb_wiki'):
         aug_train = datasets.DeviceAugment(args.img_size, train=True, dtype=aug_dtype) if raw else None
         aug_eval = datasets.DeviceAugment(args.img_size, train=False, dtype=aug_dtype) if raw else None
         dev_resize = datasets.DeviceResize(args.img_size, device) if args.gpu_resize else None     # (a pinned staging ring measured slower: tools/pinned_stager.py)
-        collate = datasets.ragged_collate if args.gpu_resize else None
+        collate = datasets.bytes_collate if args.gpu_decode else (datasets.ragged_collate if args.gpu_resize else None)
+        dev_decode = None
+        if args.gpu_decode:
+            from .jpeg import DeviceJpeg
+            dev_decode = DeviceJpeg(device, threads=args.decode_threads)
 
         # --gpu_resize hands over RAGGED file-size batches (~4x the bytes, a different size every time): pageable, like the configuration
         # bench.py's input_pipeline leg measures — a pinned pool of varying block sizes takes tens of seconds to build and fragments the host
@@ -416,7 +434,7 @@ def run(argv=None, dataset_default='imdb_wiki'):
                     return cache.batches(idx, args.batch_size, aug_train, valid=valid)
                 loader = DataLoader(_ShardSubset(train_set, idx.tolist(), valid.tolist(), with_index=cache is not None), batch_size=args.batch_size,
                                     shuffle=True, drop_last=False, **loader_kw)
-                return _loader_batches(loader, device, aug_train, dev_resize, cache)
+                return _loader_batches(loader, device, aug_train, dev_resize, cache, dev_decode)
             return batches
 
         def eval_batches(ds):
@@ -424,7 +442,7 @@ def run(argv=None, dataset_default='imdb_wiki'):
             if valid is not None:
                 ds = _ShardSubset(ds, idx.tolist(), valid.tolist())
             loader = DataLoader(ds, batch_size=args.batch_size, shuffle=False, **loader_kw)
-            return lambda: _loader_batches(loader, device, aug_eval, dev_resize)
+            return lambda: _loader_batches(loader, device, aug_eval, dev_resize, decode=dev_decode)
         steps_per_epoch = (len(shard_indices(n_train, rank, world)) + args.batch_size - 1) // args.batch_size
         n_val = (len(val_set) + args.batch_size - 1) // args.batch_size
     print(f"Training data size: {len(train_set)}")

@@ -749,6 +749,53 @@ int dir_stsb_eval(const float* pred, const float* label, long long n, const floa
                   const uint8_t* group_of_bin, double* moments, long long* ranks, void* workspace, size_t workspace_bytes,
                   dir_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * JPEG decode split at its seam: marker parsing + Huffman entropy decode on the host (csrc/dir_jpeg_host.cpp: plain C++, no GPU
+ * call, no global state, thread-safe), dequantisation + inverse DCT + chroma upsampling + YCbCr -> RGB on the GPU (csrc/dir_jpeg.hip).
+ * Bit for bit libjpeg(-turbo) as Pillow drives it (islow IDCT, fancy upsampling): np.asarray(Image.open(f).convert('RGB')).
+ *
+ * dir_jpeg_inspect: markers up to SOS.  DIR_OK: the file is TAKEN and *info is filled; DIR_EUNSUPPORTED: a JPEG this decoder does
+ *   not take (decode it elsewhere); DIR_EINVAL: not a JPEG, or cut short before its scan.  Taken: SOF0 / SOF1 with 8-bit samples
+ *   and 8-bit quantisation tables, Huffman-coded, one interleaved scan, one component or three (YCbCr: no Adobe marker, and JFIF or
+ *   component ids 1, 2, 3; luma sampling 1x1, 2x1 or 2x2, chroma 1x1), width and height <= DIR_JPEG_MAX_DIM.  Widths below 5 are
+ *   taken: the chroma upsampler then replicates, as the library's does.
+ * dir_jpeg_entropy_decode: the scan of a taken file -> quantised coefficients, int16 [ncoef / 64][64] in NATURAL (row-major, not
+ *   zig-zag) order, component after component, each component's blocks row-major over its padded grid; blocks the file never codes
+ *   do not exist (the grid is whole MCUs).  capacity counts int16 elements and must be >= info->ncoef; info must be what
+ *   dir_jpeg_inspect returned for the same bytes.  DIR_EINVAL: a truncated scan, an undecodable Huffman code, a coefficient index
+ *   past 63, a missing or malformed Huffman table, an out-of-sequence restart marker, capacity too small.  Never reads outside
+ *   [file, file + nbytes) or writes outside [coef, coef + capacity). */
+#define DIR_JPEG_MAX_DIM 8192
+typedef struct dir_jpeg_info {
+    int32_t width, height;
+    int32_t ncomp;                     /* 1 (grayscale) or 3 (YCbCr) */
+    int32_t hsamp, vsamp;              /* luma sampling factors; chroma is 1x1; 1, 1 for one component */
+    int32_t blocks_w[3], blocks_h[3];  /* per component: 8x8 blocks per row / column of the padded (whole-MCU) grid */
+    int32_t restart_interval;          /* in MCUs, 0 = none */
+    int64_t ncoef;                     /* 64 * total number of blocks */
+    uint16_t quant[3][64];             /* per component, natural order */
+} dir_jpeg_info;
+int dir_jpeg_inspect(const void* file, size_t nbytes, dir_jpeg_info* info);
+int dir_jpeg_entropy_decode(const void* file, size_t nbytes, const dir_jpeg_info* info, int16_t* coef, size_t capacity);
+/* dir_jpeg_reconstruct: B images' coefficients -> RGB pixels in the ragged `flat` buffer dir_resize_u8 consumes.  All device memory:
+ *   coef  int16 [ncoef]: the images' coefficient arrays (layout above), anywhere inside it;
+ *   quant uint16 [nslots][3][64]: per-component tables in natural order (dir_jpeg_info.quant);
+ *   table int64 [B][DIR_JPEG_ROW] = (coefficient offset in elements, byte offset of the image in flat, width, height, components,
+ *         luma hsamp, luma vsamp, quant slot); the block grid follows from width, height and sampling as in dir_jpeg_inspect;
+ *   flat  uint8 [flat_bytes]: image b is written as [height][width][3] at its byte offset; nothing else is touched;
+ *   workspace >= dir_jpeg_reconstruct_workspace(ncoef) bytes: the component planes (one byte per coefficient, plane stride =
+ *         blocks per row * 8), at the image's coefficient offset.
+ *   max_blocks / max_pixels: the largest block count / width * height of the batch (they size the two grids).
+ * The table is device memory, so the kernels check every row against ncoef, flat_bytes, nslots, max_blocks and max_pixels and leave
+ * an image that does not fit unwritten.  Two launches (dequantise + IDCT; upsample + colour), no host synchronisation, no atomics.
+ *   DIR_EINVAL: a NULL or misaligned pointer, B <= 0, a non-positive size, max_blocks * 64 > ncoef.  DIR_EUNSUPPORTED: B > 65535, max_pixels > DIR_JPEG_MAX_DIM squared.
+ *   DIR_EWORKSPACE: workspace too small. */
+#define DIR_JPEG_ROW 8
+size_t dir_jpeg_reconstruct_workspace(long long ncoef);
+int dir_jpeg_reconstruct(const int16_t* coef, long long ncoef, const uint16_t* quant, int nslots, const long long* table, int B,
+                         long long max_blocks, long long max_pixels, void* flat, long long flat_bytes, void* workspace,
+                         size_t workspace_bytes, dir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
