@@ -26,6 +26,7 @@ static inline uint64_t dir_device_setup_pending(std::atomic<uint64_t>& done) {
 
 static inline hipStream_t dir_s(dir_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline bool dir_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool dir_misaligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) != 0; }   // a = 4 or 8; NULL passes
 static inline size_t dir_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int dir_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
@@ -36,6 +37,17 @@ __device__ __forceinline__ int dir_bin_of(float l, float lo, float hi, bool has_
     if (l > hi) return has_hi ? (int)(hi - lo) : -1;
     if (l < lo) return has_lo ? 0 : -1;
     return (int)(l - lo);                        // float32 subtract, truncate (fds.py:104)
+}
+
+// The NYUD2-DIR depth bucket (nyud2-dir/models/fds.py:51-53, util.py `get_bin_idx`, loaddata.py:57-69): clamp(int(v * mult), lo, hi),
+// the float32 product truncated toward zero. Defined for every non-NaN v: a product beyond the int range (+-inf included) saturates
+// before the cast. A NaN has no bucket; every caller decides what a NaN is before it asks (FDS row -1, evaluator: pixel dropped,
+// loss: weight 1). With lo = 0 the clamp sends every product <= 0 (-0.0 and -inf among them) to bucket 0.
+__device__ __forceinline__ int dir_scaled_bucket(float v, float mult, int lo, int hi) {
+    const float x = v * mult;
+    int k = (x >= 2147483520.0f) ? 2147483647 : ((x <= -2147483520.0f) ? -2147483647 : (int)x);
+    if (k > hi) k = hi;
+    return k < lo ? lo : k;
 }
 
 __device__ __forceinline__ uint32_t dir_label_flag_bits(float l, float lo, float hi) {
@@ -68,5 +80,15 @@ __device__ __forceinline__ double dir_block_sum(double v, double* sh) {
 __device__ __forceinline__ uint32_t dir_wave_or(uint32_t v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, DIR_WAVE);
+    return v;
+}
+__device__ __forceinline__ uint32_t dir_wave_sum_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, DIR_WAVE);
+    return v;
+}
+__device__ __forceinline__ unsigned long long dir_wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, DIR_WAVE);
     return v;
 }

@@ -35,12 +35,6 @@
 static int stsb_grid(long long n) { return (int)((n + DIR_TPB - 1) / DIR_TPB); }
 static size_t stsb_gid_bytes(long long n) { return dir_align_up((size_t)n, 256); }
 
-__device__ __forceinline__ uint32_t stsb_wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, DIR_WAVE);
-    return v;
-}
-
 __global__ void __launch_bounds__(DIR_TPB)
 stsb_moments_kernel(const float* __restrict__ pred, const float* __restrict__ label, int n, const float* __restrict__ edges,
                     int num_bins, const uint8_t* __restrict__ group_of_bin, uint8_t* __restrict__ gid, double* __restrict__ partials) {
@@ -85,8 +79,8 @@ stsb_moments_kernel(const float* __restrict__ pred, const float* __restrict__ la
 #pragma unroll
     for (int gg = 0; gg < STSB_GROUPS; ++gg) {
         const bool mine = g == gg;
-        const uint32_t num = stsb_wave_sum_u32(mine ? 1u : 0u);
-        const uint32_t zer = stsb_wave_sum_u32(mine && zero ? 1u : 0u);
+        const uint32_t num = dir_wave_sum_u32(mine ? 1u : 0u);
+        const uint32_t zer = dir_wave_sum_u32(mine && zero ? 1u : 0u);
         if (lane == 0) { s_red[wave][gg * STSB_MCOLS] = (double)num; s_red[wave][gg * STSB_MCOLS + 1] = (double)zer; }
 #pragma unroll
         for (int c = 0; c < STSB_MSUMS; ++c) {
@@ -94,7 +88,7 @@ stsb_moments_kernel(const float* __restrict__ pred, const float* __restrict__ la
             if (lane == 0) s_red[wave][gg * STSB_MCOLS + 2 + c] = v;
         }
     }
-    const uint32_t bad = stsb_wave_sum_u32(g == STSB_INVALID ? 1u : 0u);
+    const uint32_t bad = dir_wave_sum_u32(g == STSB_INVALID ? 1u : 0u);
     if (lane == 0) { s_red[wave][30] = (double)bad; s_red[wave][31] = 0.0; }
     __syncthreads();
     if (threadIdx.x < STSB_MSTRIDE) {
@@ -200,9 +194,8 @@ extern "C" int dir_stsb_eval(const float* pred, const float* label, long long n,
     DIR_RETURN_IF(n <= 0 || num_bins <= 0, DIR_EINVAL);
     DIR_RETURN_IF(n > STSB_MAX_N || num_bins > STSB_MAX_BINS, DIR_EUNSUPPORTED);
     DIR_RETURN_IF(!pred || !label || !edges || !group_of_bin || !moments || !ranks || !workspace, DIR_EINVAL);
-    DIR_RETURN_IF((reinterpret_cast<uintptr_t>(pred) & 3u) || (reinterpret_cast<uintptr_t>(label) & 3u) ||
-                  (reinterpret_cast<uintptr_t>(edges) & 3u) || (reinterpret_cast<uintptr_t>(moments) & 7u) ||
-                  (reinterpret_cast<uintptr_t>(ranks) & 7u) || (reinterpret_cast<uintptr_t>(workspace) & 7u), DIR_EINVAL);
+    DIR_RETURN_IF(dir_misaligned(pred, 4) || dir_misaligned(label, 4) || dir_misaligned(edges, 4) || dir_misaligned(moments, 8) ||
+                  dir_misaligned(ranks, 8) || dir_misaligned(workspace, 8), DIR_EINVAL);
     DIR_RETURN_IF(workspace_bytes < dir_stsb_eval_workspace(n, num_bins), DIR_EWORKSPACE);
     const int grid = stsb_grid(n);
     uint8_t* gid = static_cast<uint8_t*>(workspace);

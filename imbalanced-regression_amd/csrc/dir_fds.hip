@@ -1150,15 +1150,8 @@ fds_bin_scaled_kernel(const float* __restrict__ labels, long long n, float mult,
                       int32_t* __restrict__ bins) {
     for (long long i = (long long)blockIdx.x * DIR_TPB + threadIdx.x; i < n; i += (long long)gridDim.x * DIR_TPB) {
         const float l = labels[i];
-        int b = -1;
-        if (l == l) {                                       // int(NaN) raises in the reference
-            const float v = l * mult;                       // float32 product, then truncation (fds.py:52)
-            int k = (v >= 2147483520.0f) ? 2147483647 : ((v <= -2147483520.0f) ? -2147483647 : (int)v);
-            if (k > bucket_num - 1) k = bucket_num - 1;
-            if (k < bucket_start) k = bucket_start;
-            b = k - bucket_start;
-        }
-        bins[i] = b;
+        // int(NaN) raises in the reference; otherwise the float32 product, then truncation (fds.py:52)
+        bins[i] = l == l ? dir_scaled_bucket(l, mult, bucket_start, bucket_num - 1) - bucket_start : -1;
     }
 }
 

@@ -4,39 +4,25 @@
 // here the bucket table sits in LDS and the weight map is never written.
 //
 // Per pixel, float32, one rounding per operation (-ffp-contract=off):
-//   b  = clamp(int(depth * mult), 0, bucket_num - 1)        float32 product, truncated: dir_fds_bin_scaled with bucket_start 0
+//   b  = clamp(int(depth * mult), 0, bucket_num - 1)        float32 product, truncated: dir_scaled_bucket of dir_common.h from 0
 //   w  = table[b]   (1 when there is no table, and 1 for a NaN depth)
 //   d  = pred - depth;   t = (d * d) * w;   dx = ((1 / n) * w) * (2 * d)      torch's autograd order: mean, mul, pow backward
 // A negative depth goes to bucket 0 (as PixelWeights does); the reference's Python list would wrap a negative index.  NaN propagates.
 //
 // Reduction, bit-reproducible (no float atomics anywhere):
-//   thread   float64 running sum over its pixels in index order (one aligned 16-byte quad per step, edge quads element-wise)
+//   thread   float64 running sum over its pixels in index order (one quad of the grid anchored at `depth` per step, dir_reduce_shared.h)
 //   wave     64-lane butterfly in float64
 //   block    the four wave sums added in wave order -> one float64 partial in the workspace
 //   fold     a second launch of one workgroup adds the partials in workgroup order, divides by n in float64, rounds to float32
-#include "dir_common.h"
+#include "dir_reduce_shared.h"
 
 #define DLOSS_MAX_BUCKETS 256                 // LDS: one float per bucket
 #define DLOSS_MAX_BLOCKS 256                  // one per CU; bounds the partial buffer (2 KB) and the serial fold
 
-static int dloss_grid(long long n) {
-    const long long quads = (n + 3 + 3) / 4;  // the quad grid is anchored at the 16-byte boundary below `depth`: up to 3 slots of lead-in
-    long long g = (quads + DIR_TPB - 1) / DIR_TPB;
-    if (g > DLOSS_MAX_BLOCKS) g = DLOSS_MAX_BLOCKS;
-    return g < 1 ? 1 : (int)g;
-}
-
-// min(int(depth * mult), bucket_num - 1), never below 0; the float32 product truncated (as eval_bucket of dir_eval.hip)
-__device__ __forceinline__ int dloss_bucket(float depth, float mult, int bucket_num) {
-    const float v = depth * mult;
-    int k = (v >= 2147483520.0f) ? 2147483647 : ((v <= 0.0f) ? 0 : (int)v);
-    return k > bucket_num - 1 ? bucket_num - 1 : k;
-}
-
 // one pixel: the term (d * d) * w and the unit gradient ((1 / n) * w) * (2 * d)
 __device__ __forceinline__ void dloss_pixel(float p, float z, const float* tab, float mult, int bucket_num, float inv_n, float& t, float& g) {
     float w = 1.0f;
-    if (tab && z == z) w = tab[dloss_bucket(z, mult, bucket_num)];
+    if (tab && z == z) w = tab[dir_scaled_bucket(z, mult, 0, bucket_num - 1)];
     const float d = p - z;
     t = (d * d) * w;
     g = (inv_n * w) * (2.0f * d);
@@ -56,23 +42,21 @@ depth_loss_kernel(const float* __restrict__ pred, const float* __restrict__ dept
     const int quads = (n + off + 3) / 4;
     double acc = 0.0;
     for (int q = (int)blockIdx.x * DIR_TPB + (int)threadIdx.x; q < quads; q += (int)gridDim.x * DIR_TPB) {
-        const long long i0 = 4ll * q - off;                                       // may be < 0 (lead-in) or reach past n (tail)
-        if (vec && i0 >= 0 && i0 + 3 < n) {                                       // 16-byte aligned by construction of the quad grid
-            const float4 zv = *reinterpret_cast<const float4*>(depth + i0);
-            const float4 pv = *reinterpret_cast<const float4*>(pred + i0);
-            float t[4];
-            float4 g;
-            dloss_pixel(pv.x, zv.x, tab, mult, bucket_num, inv_n, t[0], g.x);
-            dloss_pixel(pv.y, zv.y, tab, mult, bucket_num, inv_n, t[1], g.y);
-            dloss_pixel(pv.z, zv.z, tab, mult, bucket_num, inv_n, t[2], g.z);
-            dloss_pixel(pv.w, zv.w, tab, mult, bucket_num, inv_n, t[3], g.w);
+        const DirQuad<long long> d = dir_quad<long long>(q, quads, off, n);
+        if (d.full && vec) {                                                      // two 16-byte loads issued together, one 16-byte store
+            const bool all[4] = {true, true, true, true};                         // a full quad: every element exists
+            float z[4], p[4], t[4], g[4];
+            dir_quad_load(depth, d, true, all, 0.0f, z);
+            dir_quad_load(pred, d, true, all, 0.0f, p);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dloss_pixel(p[j], z[j], tab, mult, bucket_num, inv_n, t[j], g[j]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc += (double)t[j];                      // index order
-            if (dx) *reinterpret_cast<float4*>(dx + i0) = g;
+            if (dx) *reinterpret_cast<float4*>(dx + d.i0) = make_float4(g[0], g[1], g[2], g[3]);
         } else {
             for (int j = 0; j < 4; ++j) {
-                const long long i = i0 + j;
-                if (i < 0 || i >= n) continue;
+                const long long i = d.i0 + j;
+                if (i < 0 || i >= n) continue;                                    // an element outside [0, n) is skipped
                 float t, g;
                 dloss_pixel(pred[i], depth[i], tab, mult, bucket_num, inv_n, t, g);
                 acc += (double)t;
@@ -100,7 +84,7 @@ depth_loss_fold_kernel(const double* __restrict__ partials, int blocks, int n, f
 
 extern "C" size_t dir_depth_loss_workspace(long long n) {
     if (n <= 0) return 0;
-    return dir_align_up(sizeof(double) * (size_t)dloss_grid(n), 256);
+    return dir_align_up(sizeof(double) * (size_t)dir_quad_grid(n, DLOSS_MAX_BLOCKS), 256);
 }
 
 extern "C" int dir_depth_loss(const float* pred, const float* depth, long long n, float mult, const float* table, int bucket_num,
@@ -108,17 +92,14 @@ extern "C" int dir_depth_loss(const float* pred, const float* depth, long long n
     DIR_RETURN_IF(!pred || !depth || !loss || n <= 0, DIR_EINVAL);
     DIR_RETURN_IF(table && bucket_num <= 0, DIR_EINVAL);
     DIR_RETURN_IF(bucket_num > DLOSS_MAX_BUCKETS || n > 2100000000LL, DIR_EUNSUPPORTED);   // 32-bit pixel indices: split the batch
-    DIR_RETURN_IF((reinterpret_cast<uintptr_t>(pred) & 3u) || (reinterpret_cast<uintptr_t>(depth) & 3u) ||
-                  (reinterpret_cast<uintptr_t>(dx_unit) & 3u) || (reinterpret_cast<uintptr_t>(workspace) & 7u), DIR_EINVAL);
+    DIR_RETURN_IF(dir_misaligned(pred, 4) || dir_misaligned(depth, 4) || dir_misaligned(dx_unit, 4) || dir_misaligned(workspace, 8), DIR_EINVAL);
     DIR_RETURN_IF(!workspace || workspace_bytes < dir_depth_loss_workspace(n), DIR_EINVAL);
-    const int grid = dloss_grid(n);
-    // quads are anchored at the 16-byte boundary below depth[0]; 16-byte accesses when pred and dx_unit sit at the same offset from one
-    // (all three 16-byte aligned is offset 0), element-wise otherwise
-    const unsigned off = (unsigned)((reinterpret_cast<uintptr_t>(depth) >> 2) & 3u);
-    const bool vec = ((reinterpret_cast<uintptr_t>(pred) >> 2) & 3u) == off &&
-                     (!dx_unit || ((reinterpret_cast<uintptr_t>(dx_unit) >> 2) & 3u) == off);
+    const int grid = dir_quad_grid(n, DLOSS_MAX_BLOCKS);
+    // 16-byte accesses to pred and dx_unit when both sit at depth's offset (all three 16-byte aligned is offset 0), element-wise otherwise
+    const int off = dir_quad_offset(depth);
+    const bool vec = dir_quad_same_offset(pred, off) && (!dx_unit || dir_quad_same_offset(dx_unit, off));
     double* partials = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(depth_loss_kernel, dim3(grid), dim3(DIR_TPB), 0, dir_s(stream), pred, depth, (int)n, (int)off, vec, mult,
+    hipLaunchKernelGGL(depth_loss_kernel, dim3(grid), dim3(DIR_TPB), 0, dir_s(stream), pred, depth, (int)n, off, vec, mult,
                        table, bucket_num, dx_unit, partials);
     DIR_LAUNCH_CHECK();
     hipLaunchKernelGGL(depth_loss_fold_kernel, dim3(1), dim3(DIR_TPB), 0, dir_s(stream), partials, grid, (int)n, loss);

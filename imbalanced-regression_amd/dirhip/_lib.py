@@ -214,15 +214,21 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def require_device_tensor(t, dtype, name):
+def require_device_tensor(t, dtype, name, contiguous=True):
+    """``contiguous=False``: any layout passes; the caller lays the tensor out itself (the evaluators' ``.contiguous()`` / ``.reshape``)."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if not t.is_cuda:
         raise DirHipError(
-            f"{name} is on {t.device}: the FDS/LDS hot path runs only as HIP kernels on an AMD GPU "
+            f"{name} is on {t.device}: the FDS/LDS hot path and the evaluators run only as HIP kernels on an AMD GPU "
             f"(no CPU fallback). Move the tensor to the GPU.")
     if t.dtype != dtype:
         raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
     return t
+
+
+def require_device_f32(t, name):
+    """The evaluators' input check: a float32 GPU tensor of any layout; each evaluator lays it out itself."""
+    return require_device_tensor(t, torch.float32, name, contiguous=False)

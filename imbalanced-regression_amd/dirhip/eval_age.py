@@ -17,13 +17,14 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._eval_table import TableEvaluator
 
 COLUMNS = ("SE", "AE", "LN", "ZERO", "NUM")        # column order of the device table
 SHOTS = ("many", "median", "low")
 MAX_ROWS = 256                                     # the kernel's LDS layout: num_labels + 1 <= 256
 
 
-class ShotEvaluator:
+class ShotEvaluator(TableEvaluator):
     def __init__(self, train_labels, many_shot_thr=100, low_shot_thr=20):
         # train.py:340, :350-357: the training labels cast with astype(int), a label's shot by its count among them
         train = np.array(train_labels).astype(int).reshape(-1)
@@ -36,30 +37,12 @@ class ShotEvaluator:
                                 f"label rows (no CPU fallback)")
         counts = np.append(self.train_hist, 0)                                     # the "other" row: no training sample has such a label
         self.shot_of_row = np.where(counts > many_shot_thr, "many", np.where(counts < low_shot_thr, "low", "median"))
-        self.table = None                      # [num_labels + 1, 5] float64 on the device of the first call
-
-    def _table_on(self, device):
-        if self.table is None:
-            self.table = torch.zeros(self.num_labels + 1, len(COLUMNS), dtype=torch.float64, device=device)
-        elif self.table.device != device:
-            raise L.DirHipError(f"ShotEvaluator holds its table on {self.table.device}, got tensors on {device}")
-        return self.table
-
-    @staticmethod
-    def _device_f32(t, name):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-        if not t.is_cuda:
-            raise L.DirHipError(f"{name} is on {t.device}: the evaluator runs only as a HIP kernel on an AMD GPU (no CPU fallback). "
-                                f"Move the tensor to the GPU.")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-        return t.contiguous()
+        super().__init__(self.num_labels + 1, len(COLUMNS), first="update")
 
     def update(self, preds, labels, valid=None):
         """``preds`` / ``labels``: float32 GPU tensors of equal element count ([B] or [B, 1]); ``valid`` (bool / uint8, same count):
         samples to keep, e.g. False at the wrap-around padding of ``parallel.shard_indices``. Enqueue only."""
-        preds, labels = self._device_f32(preds, "preds"), self._device_f32(labels, "labels")
+        preds, labels = L.require_device_f32(preds, "preds").contiguous(), L.require_device_f32(labels, "labels").contiguous()
         if preds.numel() != labels.numel():
             raise ValueError(f"preds and labels differ in size: {preds.numel()} vs {labels.numel()}")
         if valid is not None:
@@ -72,20 +55,6 @@ class ShotEvaluator:
             valid = valid.contiguous()
         if labels.numel():
             ops.age_eval_accumulate(preds, labels, valid, self._table_on(labels.device))
-
-    def reset(self):
-        if self.table is not None:
-            self.table.zero_()
-
-    def merge_across_ranks(self, group=None):
-        """Sum the table over the ranks of ``group`` (a validation set sharded over the one-process-per-GPU engine): afterwards
-        ``results()`` returns the same dict on every rank. No-op without an initialised process group."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-            return
-        if self.table is None:
-            raise L.DirHipError("merge_across_ranks before the first update: the table's device is not known yet")
-        dist.all_reduce(self.table, group=group)
 
     @staticmethod
     def _metrics(row):

@@ -17,11 +17,12 @@ import torch
 
 from . import _lib as L
 from . import ops
+from ._eval_table import TableEvaluator
 
 COLUMNS = ("MSE", "MAE", "ABS_REL", "LG10", "DELTA1", "DELTA2", "DELTA3", "NUM")        # column order of the device table
 
 
-class Evaluator:
+class Evaluator(TableEvaluator):
     def __init__(self, bucket_num=100, mult=10.0):
         # nyud2-dir/util.py:37-43: depth buckets (0.1 m) by the number of training pixels they hold
         self.shot_idx = {
@@ -32,30 +33,12 @@ class Evaluator:
                     78, 79, 80, 81, 82, 83, 84, 85, 86, 87, 88, 89, 90, 91, 92, 93, 94, 95, 96, 97, 98, 99]
         }
         self.bucket_num, self.mult = int(bucket_num), float(mult)
-        self.table = None                      # [bucket_num, 8] float64 on the device of the first call
-
-    def _table_on(self, device):
-        if self.table is None:
-            self.table = torch.zeros(self.bucket_num, 8, dtype=torch.float64, device=device)
-        elif self.table.device != device:
-            raise L.DirHipError(f"Evaluator holds its table on {self.table.device}, got tensors on {device}")
-        return self.table
-
-    @staticmethod
-    def _device_f32(t, name):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-        if not t.is_cuda:
-            raise L.DirHipError(f"{name} is on {t.device}: the evaluator runs only as a HIP kernel on an AMD GPU (no CPU fallback). "
-                                f"Move the tensor to the GPU.")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-        return t.contiguous()
+        super().__init__(self.bucket_num, len(COLUMNS))
 
     def __call__(self, output, depth):
         """The reference's call form: two tensors of equal element count (``output[mask], depth[mask]`` in test.py). Enqueue only."""
-        output = self._device_f32(output, "output").view(1, 1, -1)
-        depth = self._device_f32(depth, "depth").view(1, 1, -1)
+        output = L.require_device_f32(output, "output").contiguous().view(1, 1, -1)
+        depth = L.require_device_f32(depth, "depth").contiguous().view(1, 1, -1)
         if output.numel() != depth.numel():
             raise ValueError(f"output and depth differ in size: {output.numel()} vs {depth.numel()}")
         if depth.numel():
@@ -65,7 +48,7 @@ class Evaluator:
         """Fused form of test.py:52-54: ``pred`` [N, 1, h, w] (or [N, h, w]) is the network output, ``depth`` [N, 1, H, W] the ground
         truth, ``mask`` (bool / uint8, depth's shape) the pixels to keep. Equivalent to
         ``self(F.interpolate(pred, (H, W), mode='bilinear', align_corners=True)[mask], depth[mask])`` without any of the intermediates."""
-        pred, depth = self._device_f32(pred, "pred"), self._device_f32(depth, "depth")
+        pred, depth = L.require_device_f32(pred, "pred").contiguous(), L.require_device_f32(depth, "depth").contiguous()
         if pred.dim() == 4 and pred.shape[1] == 1:
             pred = pred[:, 0]
         if depth.dim() == 4 and depth.shape[1] == 1:
@@ -81,20 +64,6 @@ class Evaluator:
         if pred.dim() != 3 or depth.dim() != 3:
             raise ValueError(f"pred / depth must be [N, 1, h, w] / [N, 1, H, W], got {tuple(pred.shape)} / {tuple(depth.shape)}")
         ops.depth_eval_accumulate(pred, depth, mask, self._table_on(depth.device), self.mult)
-
-    def reset(self):
-        if self.table is not None:
-            self.table.zero_()
-
-    def merge_across_ranks(self, group=None):
-        """Sum the table over the ranks of ``group`` (a test set sharded over the one-process-per-GPU engine): afterwards
-        ``evaluate_shot()`` returns the same dict on every rank. No-op without an initialised process group."""
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
-            return
-        if self.table is None:
-            raise L.DirHipError("merge_across_ranks before the first call: the table's device is not known yet")
-        dist.all_reduce(self.table, group=group)
 
     @staticmethod
     def get_bin_idx(x):

@@ -91,20 +91,9 @@ class STSShotAverage:
             return self._num_bins - 1
         return int(np.where(self._edges_host > label)[0][0]) - 1
 
-    @staticmethod
-    def _device_f32(t, name):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-        if not t.is_cuda:
-            raise L.DirHipError(f"{name} is on {t.device}: the evaluator runs only as HIP kernels on an AMD GPU (no CPU fallback). "
-                                f"Move the tensor to the GPU.")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-        return t.detach().reshape(-1)
-
     def __call__(self, pred, label):
         """``pred`` / ``label``: float32 GPU tensors of equal element count ([B] or [B, 1]). Appends; enqueue only."""
-        pred, label = self._device_f32(pred, "pred"), self._device_f32(label, "label")
+        pred, label = L.require_device_f32(pred, "pred").detach().reshape(-1), L.require_device_f32(label, "label").detach().reshape(-1)
         if pred.numel() != label.numel():
             raise ValueError(f"pred and label differ in size: {pred.numel()} vs {label.numel()}")
         if pred.device != label.device:

@@ -18,6 +18,32 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+_STREAM_WS = {}
+
+
+def _stream_ws(nbytes, dev):
+    """The workspace of the streaming reductions (depth loss and the three evaluators), kept per (device, stream) and grown on
+    demand. These calls never overlap on one stream and the stream orders the reuse, so they share one buffer."""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = _STREAM_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _STREAM_WS[key] = _ws(nbytes, dev)
+    return ws
+
+
+def _mask_u8(mask, name, like, like_name, same_shape):
+    """Optional bool / uint8 keep mask -> None or a contiguous uint8 tensor on ``like``'s device with its shape (``same_shape``) or
+    its element count. A bool mask is viewed, not copied: same bytes, no kernel."""
+    if mask is None:
+        return None
+    if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    mask = L.require_device_tensor(mask, torch.uint8, name)
+    if mask.device != like.device or (mask.shape != like.shape if same_shape else mask.numel() != like.numel()):
+        raise ValueError(f"{name} must have {like_name}'s {'shape' if same_shape else 'element count'} and device")
+    return mask
+
+
 # ---- K1 -------------------------------------------------------------------------------------------
 def label_flags(labels, bucket_start, bucket_num, flags=None):
     labels = L.require_device_tensor(labels, f32, "labels")
@@ -223,13 +249,10 @@ def scale_by_device_scalar(t, scalar):
 
 
 # ---- NYUD2-DIR training loss -----------------------------------------------------------------------
-_LOSS_WS = {}
-
-
 def depth_loss(pred, depth, table, mult, need_grad):
     """pred, depth f32 device tensors of equal numel (contiguous, any shape), table [bucket_num] f32 on that device or None
     -> (loss 0-dim f32, dx_unit of pred's shape or None). One streaming launch + a one-workgroup fold; enqueue only, no sync.
-    The 2 KB workspace is kept per (device, stream): reuse is ordered by the stream."""
+    The 2 KB workspace is ``_stream_ws``'s."""
     pred = L.require_device_tensor(pred, f32, "pred")
     depth = L.require_device_tensor(depth, f32, "depth")
     dev = pred.device
@@ -242,24 +265,17 @@ def depth_loss(pred, depth, table, mult, need_grad):
     n = pred.numel()
     loss = torch.empty((), dtype=f32, device=dev)
     dx = torch.empty_like(pred) if need_grad else None
-    nbytes = L.lib().dir_depth_loss_workspace(n)
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _LOSS_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _LOSS_WS[key] = _ws(nbytes, dev)
+    ws = _stream_ws(L.lib().dir_depth_loss_workspace(n), dev)
     L.check(L.lib().dir_depth_loss(L.ptr(pred), L.ptr(depth), n, float(mult), L.ptr(table), table.numel() if table is not None else 0,
                                    L.ptr(loss), L.ptr(dx), L.ptr(ws), ws.numel(), L.stream_ptr(dev)), "dir_depth_loss")
     return loss, dx
 
 
 # ---- NYUD2-DIR evaluation -------------------------------------------------------------------------
-_EVAL_WS = {}
-
-
 def depth_eval_accumulate(pred, depth, mask, table, mult=10.0):
     """pred [N, h, w] f32, depth [N, H, W] f32, mask [N, H, W] uint8 / bool or None, table [bucket_num, 8] f64 (accumulated into).
     One fused pass (bilinear align-corners upsampling of ``pred`` in registers when the sizes differ); enqueue only, no sync.
-    The workspace is kept per (device, stream) and grown on demand: reuse is ordered by the stream."""
+    The workspace is ``_stream_ws``'s."""
     pred = L.require_device_tensor(pred, f32, "pred")
     depth = L.require_device_tensor(depth, f32, "depth")
     table = L.require_device_tensor(table, f64, "table")
@@ -270,23 +286,14 @@ def depth_eval_accumulate(pred, depth, mask, table, mult=10.0):
     dev = depth.device
     if pred.device != dev or table.device != dev:
         raise ValueError("pred, depth and table must live on one device")
-    if mask is not None:
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)                       # same bytes, no kernel
-        mask = L.require_device_tensor(mask, torch.uint8, "mask")
-        if mask.shape != depth.shape or mask.device != dev:
-            raise ValueError("mask must have depth's shape and device")
+    mask = _mask_u8(mask, "mask", depth, "depth", True)
     n, h, w = pred.shape
     _, H, W = depth.shape
     nb = table.shape[0]
     per = max(1, 2_000_000_000 // max(H * W, h * w))            # the C-ABI indexes pixels with 32 bits: split very large batches
     for a in range(0, n, per):
         k = min(per, n - a)
-        nbytes = L.lib().dir_depth_eval_workspace(k * H * W, nb)
-        key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-        ws = _EVAL_WS.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = _EVAL_WS[key] = _ws(nbytes, dev)
+        ws = _stream_ws(L.lib().dir_depth_eval_workspace(k * H * W, nb), dev)
         L.check(L.lib().dir_depth_eval_accumulate(L.ptr(pred[a:a + k]), L.ptr(depth[a:a + k]), L.ptr(mask[a:a + k]) if mask is not None else None,
                                                   k, h, w, H, W, float(mult), nb, L.ptr(table), L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
                 "dir_depth_eval_accumulate")
@@ -308,18 +315,9 @@ def age_eval_accumulate(pred, label, valid, table):
     dev = label.device
     if pred.device != dev or table.device != dev:
         raise ValueError("pred, label and table must live on one device")
-    if valid is not None:
-        if isinstance(valid, torch.Tensor) and valid.dtype == torch.bool:
-            valid = valid.view(torch.uint8)                     # same bytes, no kernel
-        valid = L.require_device_tensor(valid, torch.uint8, "valid")
-        if valid.numel() != label.numel() or valid.device != dev:
-            raise ValueError("valid must have label's element count and device")
+    valid = _mask_u8(valid, "valid", label, "label", False)
     n, num_labels = label.numel(), table.shape[0] - 1
-    nbytes = L.lib().dir_age_eval_workspace(n, num_labels)
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _EVAL_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _EVAL_WS[key] = _ws(nbytes, dev)
+    ws = _stream_ws(L.lib().dir_age_eval_workspace(n, num_labels), dev)
     L.check(L.lib().dir_age_eval_accumulate(L.ptr(pred), L.ptr(label), L.ptr(valid), n, num_labels, L.ptr(table), L.ptr(ws), ws.numel(),
                                             L.stream_ptr(dev)), "dir_age_eval_accumulate")
     return table
@@ -344,11 +342,7 @@ def stsb_eval(pred, label, edges, group_of_bin):
     if pred.device != dev or edges.device != dev or group_of_bin.device != dev:
         raise ValueError("pred, label, edges and group_of_bin must live on one device")
     n = label.numel()
-    nbytes = L.lib().dir_stsb_eval_workspace(n, num_bins)
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
-    ws = _EVAL_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _EVAL_WS[key] = _ws(nbytes, dev)
+    ws = _stream_ws(L.lib().dir_stsb_eval_workspace(n, num_bins), dev)
     both = torch.empty(60, dtype=torch.int64, device=dev)
     moments, ranks = both[:40].view(f64).view(4, 10), both[40:].view(4, 5)
     L.check(L.lib().dir_stsb_eval(L.ptr(pred), L.ptr(label), n, L.ptr(edges), num_bins, L.ptr(group_of_bin), L.ptr(moments), L.ptr(ranks),

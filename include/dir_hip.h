@@ -661,7 +661,8 @@ int dir_dropout_mask(uint64_t seed, uint64_t offset, double p, int B, int C, uin
  *   (h, w) != (H, W): the prediction is upsampled bilinearly with align_corners=True at every target pixel, in registers
  *   (float32 steps: s = i * ((in - 1) / (out - 1)), i0 = min(int(s), in - 1), l = s - i0, value = hy * (hx * v00 + lx * v01) +
  *   ly * (hx * v10 + lx * v11)); the upsampled map is never written.  A pixel whose depth is NaN is skipped.
- *   Per kept pixel, float32, one rounding per operation: bucket = min(int(depth * mult), bucket_num - 1) (depth <= 0 -> 0),
+ *   Per kept pixel, float32, one rounding per operation: bucket = min(int(depth * mult), bucket_num - 1) (depth <= 0 -> 0; the rule
+ *   of dir_fds_bin_scaled with bucket_start 0, one device function serves both and dir_depth_loss),
  *   d = |pred - depth|, r = pred / depth unless that is < depth / pred (a NaN ratio stays NaN); the bucket's row of
  *   table [bucket_num][8] f64 gains  d*d, d, d / depth, |log(pred) / ln10 - log(depth) / ln10|, [r <= 1.25], [r <= 1.5625],
  *   [r <= 1.953125], 1.  Non-positive predictions put the reference's NaN / inf into the LG10 column; nothing is clamped.
@@ -699,7 +700,8 @@ int dir_age_eval_accumulate(const float* pred, const float* label, const uint8_t
  *   pred, depth [n] f32 (n = B * H * W, any 4-byte aligned pointers), table [bucket_num] f32 or NULL (reweight == 'none': weight 1),
  *   loss [1] f32, dx_unit [n] f32 or NULL (no gradient wanted).
  *   Per pixel, float32, one rounding per operation (no fused multiply-add):
- *     b = clamp(int(depth * mult), 0, bucket_num - 1)   (float32 product, truncated: dir_fds_bin_scaled with bucket_start 0)
+ *     b = clamp(int(depth * mult), 0, bucket_num - 1)   (float32 product, truncated: the device function behind dir_fds_bin_scaled,
+ *                                                        with bucket_start 0)
  *     w = table[b]   (1 for a NaN depth);   d = pred - depth;   t = (d * d) * w
  *     dx_unit = ((1 / n) * w) * (2 * d),  1 / n = 1.0f / (float)n   (torch's autograd order: mean, mul, pow backward)
  *   A negative depth goes to bucket 0 (as dirhip.lds_nyud2.PixelWeights); the reference's Python list would wrap a negative index.

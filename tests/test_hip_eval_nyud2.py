@@ -141,6 +141,64 @@ def test_nan_depths_and_non_positive_predictions():
     assert np.array_equal(got[10:15, 4:7], np.repeat(neg[:, None], 3, axis=1)) and neg.sum() > 0 and (p == 0).sum() > 0
 
 
+# ---- one bucket rule: the FDS binning, the evaluator and the training loss against the restatement's ------------------------------------
+def bucket_rule_depths(mult):
+    """float32 depths on and next to every bucket edge k / mult (k = 0..260), the zeros, negatives, the int range's ends, +-inf and
+    the smallest denormal; four copies in a seeded order, so that the vector spans several workgroups and mixes buckets in a wave."""
+    f32 = np.float32
+    edges = (np.arange(261, dtype=f32) / f32(mult)).astype(f32)
+    special = np.array([0.0, -0.0, -1e-3, -0.5, -1.0, -7.3, -1e31, 1e31, np.inf, -np.inf, 1.4e-45], f32)
+    z = np.concatenate([edges, np.nextafter(edges, f32(-np.inf)), np.nextafter(edges, f32(np.inf)), special]).astype(f32)
+    return np.random.default_rng(11).permutation(np.tile(z, 4))
+
+
+@pytest.mark.parametrize("mult,bucket_num", [(10.0, 100), (0.5, 7), (20.0, 256)])
+def test_three_callers_of_the_bucket_rule_agree_with_the_restatement(mult, bucket_num):
+    """``dir_fds_bin_scaled``, the NUM column of ``dir_depth_eval_accumulate`` and the weight lookup of ``dir_depth_loss`` put every
+    depth into the bucket ``nyud2_eval_reference.bucket_of`` restates: all comparisons exact (integers, and float32 arithmetic
+    restated operation by operation)."""
+    from dirhip import ops
+    from test_nyud2_loss_host import restate
+    f32 = np.float32
+    # inputs and the three expectations, on the CPU
+    z = bucket_rule_depths(mult)
+    assert z.dtype == f32 and not np.isnan(z).any() and 3000 < z.size < 5000
+    want_bins = R.bucket_of(z, mult, bucket_num)
+    want_num = np.bincount(want_bins, minlength=bucket_num)
+    with np.errstate(all="ignore"):
+        prod = z * f32(mult)
+    assert (prod <= -1).any() and (prod >= bucket_num).any()                                   # both clamps are hit
+    if (mult, bucket_num) == (10.0, 100):
+        assert (want_num > 0).all()                                                            # every bucket occurs
+    fin = np.isfinite(z) & (np.abs(z) < 1e15)
+    zl = z[fin]
+    pl = (zl * f32(1.25) + f32(0.125)).astype(f32)
+    wtab = np.arange(1, bucket_num + 1, dtype=f32)                                             # table[b] = b + 1: the weight names the bucket
+    want_dx = ((f32(1) / f32(zl.size)) * wtab[want_bins[fin]]) * (f32(2) * (pl - zl))
+    assert want_dx.dtype == f32 and np.array_equal(restate(pl, zl, wtab, mult)["dx"], want_dx)  # the loss tests' restatement: same rule
+    # the device
+    zd = dev(z)
+    assert np.array_equal(ops.bin_scaled(zd, mult, 0, bucket_num).cpu().numpy(), want_bins)
+    got = run_table(zd.view(1, 1, -1), zd.view(1, 1, -1), None, bucket_num, mult)
+    assert np.array_equal(got[:, 7], want_num)
+    _, dx = ops.depth_loss(dev(pl), dev(zl), dev(wtab), mult, True)
+    assert np.array_equal(dx.cpu().numpy().view(np.uint32), want_dx.view(np.uint32))
+    # NaN depths have no bucket: FDS row -1 and not counted. The loss's weight for them cannot be seen on the device (d = pred - NaN
+    # makes the term and dx_unit NaN whatever the weight): the loss part pins only that the finite pixels keep their weights, that
+    # NaN comes out exactly where the depth is NaN, and that the call does not fault on a NaN bucket
+    zn = np.array([np.nan, 0.35, np.nan, np.nan, 4.0, np.nan, np.nan], f32)
+    pn = np.full(zn.size, 2.0, f32)
+    bins = ops.bin_scaled(dev(zn), mult, 0, bucket_num).cpu().numpy()
+    assert np.array_equal(bins, np.where(np.isnan(zn), -1, R.bucket_of(zn, mult, bucket_num)))
+    got = run_table(dev(pn).view(1, 1, -1), dev(zn).view(1, 1, -1), None, bucket_num, mult)
+    assert got[:, 7].sum() == 2 and np.isfinite(got).all()
+    assert not run_table(dev(pn[:1]).view(1, 1, -1), dev(zn[:1]).view(1, 1, -1), None, bucket_num, mult).any()
+    loss, dx = ops.depth_loss(dev(pn), dev(zn), dev(wtab), mult, True)
+    want = restate(pn, zn, wtab, mult)
+    assert want["w"][np.isnan(zn)].tolist() == [1.0] * 5 and np.isnan(loss.item())            # the weight 1 is the restatement's
+    assert np.array_equal(dx.cpu().numpy(), want["dx"], equal_nan=True) and np.isnan(want["dx"]).sum() == 5
+
+
 # ---- each bar rejects a plausible defect, emulated on the restatement ----------------------------------------------------------------
 def test_bars_reject_emulated_defects():
     rng = np.random.default_rng(7)
@@ -259,7 +317,7 @@ def test_fused_form_launches_only_the_two_library_kernels():
         torch.cuda.synchronize()
     kernels = [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower()]
     print(sorted(set(kernels)))
-    assert len(kernels) == 6 and all("depth_eval" in k for k in kernels), kernels
+    assert len(kernels) == 6 and all("depth_eval" in k or "dir_table_fold" in k for k in kernels), kernels
     assert not any(("Memcpy" in e.name or "memcpy" in e.name) for e in prof.events())
 
 
