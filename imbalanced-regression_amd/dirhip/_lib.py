@@ -138,6 +138,11 @@ SIGNATURES = {
     "dir_tail_dropout_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]
                              + [c_uint64, c_uint64, c_double, c_void_p]),
     "dir_dropout_mask": (c_int, [c_uint64, c_uint64, c_double, c_int, c_int, c_void_p, c_void_p]),
+    "dir_pair_tail_workspace": (c_size_t, [c_int, c_int]),
+    "dir_pair_tail_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_int] + [c_void_p] * 5 + [c_uint64, c_uint64, c_uint64, c_double]
+                          + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "dir_pair_tail_bwd": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 6 + [c_int] * 4 + [c_uint64, c_uint64, c_uint64, c_double]
+                          + [c_void_p] * 5 + [c_size_t, c_void_p]),
     "dir_depth_eval_workspace": (c_size_t, [c_longlong, c_int]),
     "dir_depth_eval_accumulate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
                                           c_void_p, c_void_p, c_size_t, c_void_p]),

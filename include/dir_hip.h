@@ -656,6 +656,53 @@ int dir_tail_dropout_bwd(const float* dpred, const float* dencoding, const int32
 int dir_dropout_mask(uint64_t seed, uint64_t offset, double p, int B, int C, uint8_t* keep, dir_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Fused STS-B-DIR pair head: HeadlessPairEncoder.forward after the LSTM and MultiTaskModel.forward up to the loss
+ * (sts-b-dir/models.py:155-166 and :84-92; FDS.smooth of sts-b-dir/fds.py:127-141), float32, and its backward.
+ *   s1 [B, T1, D], s2 [B, T2, D] f32 contiguous; mask1 [B, T1], mask2 [B, T2] uint8 (non-zero = a token; any pattern, not only
+ *   prefixes); weight [4D], bias [1] f32.
+ *   calibration: bins [B] int32 (table row of the sample, dir_fds_bin_edges; < 0 or >= nb = row untouched) and m1 / scale / m2
+ *   [nb, 4D] f32 (scale from dir_fds_prepare_scale_ex) — all four or none (NULL: epoch < start_smooth, eval mode, FDS off).
+ *   dropout (models.py:155-156, nn.Dropout(p) on both encodings, training only): the Philox rule stated above for dir_tail_dropout_*,
+ *   same counter and key construction, same threshold, with e = (b * Ti + t) * D + d the element of sentence i, offset1 for sentence 1
+ *   and offset2 for sentence 2: x' = keep(e) ? x * (float)(1 / (1 - p)) : 0.  p == 0: no dropout (x' = x, no random number is drawn).
+ *   It is not nn.Dropout's random stream.
+ * dir_pair_tail_fwd, per sample b and column d, one float32 rounding per operation:
+ *   u = max over t with mask1[b, t] != 0 of s1'[b, t, d], v likewise from sentence 2 (models.py:161-164).  A NaN at an unmasked
+ *   position makes the maximum NaN (torch.max); a NaN at a masked position is never looked at.
+ *   arg1 / arg2 [B, D] int32: the lowest t that attains the maximum, or the lowest unmasked t that holds a NaN.  No unmasked position:
+ *   u = -inf, arg = -1 (rows are read, masked or not, but never outside the tensors).
+ *   f = [u, v, |u - v|, u * v] (models.py:166), then emb[b, k] = scale[bin, k] < 0 ? f[k] : (f[k] - m1[bin, k]) * scale[bin, k] + m2[bin, k]
+ *   (= dir_fds_calibrate_fwd on f).  emb [B, 4D] is stored once, CALIBRATED: the reference calibrates in place, so its out['embs']
+ *   is this tensor.  uv [B, 2D] = the raw [u, v], saved for the backward.
+ *   logits[b] = sum_k emb[b, k] * weight[k] + bias: per thread over its 16 elements, wavefront butterfly, one partial per 256-column
+ *   tile in `workspace`, tiles added in order by a second launch, then the bias.  Fixed order, no atomics.
+ * dir_pair_tail_bwd: g[k] = dlogits[b] * weight[k] (+ demb[b, k] when demb != NULL); where the forward calibrated with scale >= 0,
+ *   g[k] *= scale[bin, k].  With g = [g_u, g_v, g_a, g_m] and sg = sign(u - v), sign(0) = 0 (0 for a NaN):
+ *     du = (g_u + sg * g_a) + g_m * v,   dv = (g_v - sg * g_a) + g_m * u      (this order of operations)
+ *   ds1[b, t, d] = (t == arg1[b, d]) ? drop'(du) : 0, drop' = times the keep factor of THAT element, 0 if it was dropped; ds2 likewise
+ *   from dv and arg2.  One streaming launch writes every element of ds1 and ds2 (no memset + scatter; the [B, 4D] gradient is never
+ *   materialised).  ds1 / ds2 NULL = skip that tensor.  Pass the forward's bins / nb / scale (NULL, 0, NULL without calibration),
+ *   seed / offsets / p, uv, arg1, arg2.
+ *   dweight [4D] = sum_b dlogits[b] * emb[b, k], dbias [1] = sum_b dlogits[b] (dweight NULL = skip both; dbias NULL = skip it): the
+ *   fixed-order two-stage reduction of dir_tail_bwd; needs emb and the workspace.
+ * Any D >= 1: 16-byte accesses when D % 4 == 0 and every pointer is 16-byte aligned, element-wise otherwise, same results.
+ * workspace >= dir_pair_tail_workspace(B, D) bytes (one size serves both directions; 0 for unsupported arguments).
+ * All argument checks happen before any HIP call:
+ *   DIR_EINVAL: a NULL required pointer, B, T1, T2 or D not positive, p outside [0, 1] (NaN included), the calibration pointers only
+ *   partly given (or nb <= 0 with them).  DIR_EUNSUPPORTED: B * max(T1, T2) * D or B * 4D at or beyond 2^31, B > 65535 (grid).
+ *   DIR_EWORKSPACE: workspace missing or too small. */
+size_t dir_pair_tail_workspace(int B, int D);
+int dir_pair_tail_fwd(const float* s1, const float* s2, const uint8_t* mask1, const uint8_t* mask2, int B, int T1, int T2, int D,
+                      const int32_t* bins, int nb, const float* m1, const float* scale, const float* m2,
+                      const float* weight, const float* bias, uint64_t seed, uint64_t offset1, uint64_t offset2, double p,
+                      float* emb, float* uv, int32_t* arg1, int32_t* arg2, float* logits, void* workspace, size_t workspace_bytes,
+                      dir_stream_t stream);
+int dir_pair_tail_bwd(const float* dlogits, const float* demb, const int32_t* bins, int nb, const float* scale, const float* weight,
+                      const float* emb, const float* uv, const int32_t* arg1, const int32_t* arg2, int B, int T1, int T2, int D,
+                      uint64_t seed, uint64_t offset1, uint64_t offset2, double p, float* ds1, float* ds2, float* dweight,
+                      float* dbias, void* workspace, size_t workspace_bytes, dir_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * NYUD2-DIR balanced depth evaluation (nyud2-dir/util.py:35-133 `Evaluator`, nyud2-dir/test.py:39-59) in one streaming pass.
  *   pred [N, h, w] f32 (the network output), depth [N, H, W] f32, mask [N, H, W] uint8 (non-zero = keep; NULL = every pixel).
  *   (h, w) != (H, W): the prediction is upsampled bilinearly with align_corners=True at every target pixel, in registers
